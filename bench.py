@@ -8,11 +8,11 @@ N > 1: one process per GPU over RCCL.  Under torchrun (RANK / WORLD_SIZE set) th
 one rank; launched plainly, the parent starts `python -m torch.distributed.run` with N
 children BEFORE it touches the GPU, relays rank 0's JSON line and exits with their code.
 Every rank owns `--pairs` image pairs (weak scaling).  Default step by N:
-  N = 1  --step ops   : the hot-path ops alone (below): the headline, with roofline and cpu_baseline
+  N = 1  --step ops   : the hot-path ops alone (below): the headline (roofline and cpu_baseline with --full)
   N > 1  --step model : one TRAINING step of the host model (HRNetV2-W32 backbone + PWC flow head, unFlowLoss,
                         backward, Adam) under DistributedDataParallel over RCCL: 122 MB of gradients all-reduced
                         inside every step -- the step data-parallel scaling is judged on; read it against
-                        `extra.model_step` of the N = 1 line (the same step on one GPU)
+                        `extra.model_step` of the N = 1 --full line (the same step on one GPU)
 `--step ops` at N > 1 reports the op-only rate of the N ranks (the ops have no parameters: no collective
 belongs to them) with the model-sized exchange timed beside it as `gradient_exchange`; `--step head` is the
 flow head alone under DDP.  Every N > 1 line carries `single_gpu_step` and `scaling_efficiency` = value /
@@ -32,13 +32,17 @@ directions and all four pyramid levels, in the order PWCNetHead issues them
 Inputs are synthetic (portable hash generator), resident in HBM before the
 timed region.  The timed region replays the whole step from a hipGraph
 (captured through torch.cuda.CUDAGraph; --no-graph launches eagerly).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline.  With
+`--full` the JSON line also carries
   roofline     : achieved algorithmic GB/s of the dominant kernel, measured
                  live with HIP events on the launch stream, vs the 8 TB/s HBM peak
   cpu_baseline : the reference's pure-PyTorch CPU correlation (oracle port of
                  CorrelationTorch, correlation.py:4-21) fwd+bwd on the same
-                 pyramid, timed on this box's host cores on a bounded sample.
+                 pyramid, timed on this box's host cores on a bounded sample
+and the steady-state, after-idle and stock-PyTorch GPU passes and the extra
+configurations (extra.*) of the op step.
 """
 import argparse
 import json
@@ -120,6 +124,28 @@ class Workload:
                 fused.append({k: (torch.cat([a[k], b[k]], 0) if a[k] is not None else None)
                               for k in ("f1", "f2", "gout", "flow")})
             self.dirs = [fused]
+        # what the last step handed its caller, by (direction tag, level, what): see _record() and outputs()
+        self.results = {}
+        self.tags = {id(lv): ("both" if fuse else "d%d" % i) for i, lv in enumerate(self.dirs)}
+
+    def _record(self, lv, l, **arrays):
+        tag = self.tags.get(id(lv))
+        if tag is not None:
+            for what, t in arrays.items():
+                self.results[(tag, l, what)] = t
+
+    def outputs(self, results=None):
+        """{name: tensor} of what one step hands its caller (`results`: a copy of self.results taken earlier): per
+        flow direction d<i> and level L<l> the correlation output `corr`, the warped image `warped`, and the
+        gradients `grad_f1`, `grad_f2`, `grad_flow` of the step's inputs.  A launch that carries both directions
+        (stacked levels, --fuse-directions) is split back into them: direction 0 is the first half of its batch."""
+        out = {}
+        for (tag, l, what), t in sorted((self.results if results is None else results).items()):
+            halves = t.shape[0] // 2
+            parts = [("d0", t[:halves]), ("d1", t[halves:])] if tag == "both" else [(tag, t)]
+            for d, part in parts:
+                out["%s_L%d_%s" % (d, l, what)] = part
+        return out
 
     def kernels(self):
         """(label, algorithmic bytes) of every launch of one direction (or of the fused call)."""
@@ -149,6 +175,8 @@ class Workload:
                 t["warped"] = t["f2"]
             if skip != "corr_fwd_L%d" % l:
                 t["out"] = ops.correlation(t["f1"], t["warped"], *CORR_P)
+            if skip is None:
+                self._record(lv, l, corr=t["out"], **({"warped": t["warped"]} if l > 0 else {}))
             if l == 0 and after_first is not None:
                 after_first()          # (the other direction's stream forks here: see step())
         # backward, fine to coarse
@@ -158,13 +186,17 @@ class Workload:
                 g1, g2 = ops.correlation_backward(t["f1"], t["warped"], t["gout"], *CORR_P)
                 keep.append(g1)
             else:
-                g2 = t["f1"]
+                g1, g2 = None, t["f1"]
             if l > 0:
                 if skip != "warp_bwd_L%d" % l:
-                    keep += ops.flow_warp_backward_ctx(t["f2"], t["flow"], t["ctx"], g2, 1, 0,
-                                                       True, True)
+                    gi, gf = ops.flow_warp_backward_ctx(t["f2"], t["flow"], t["ctx"], g2, 1, 0, True, True)
+                    keep += [gi, gf]
+                    if skip is None:
+                        self._record(lv, l, grad_f1=g1, grad_f2=gi, grad_flow=gf)
             else:
                 keep.append(g2)
+                if skip is None:
+                    self._record(lv, l, grad_f1=g1, grad_f2=g2)
 
     def _levels_fwd(self, lv, levels):
         ops = torch.ops.cerberus
@@ -175,6 +207,7 @@ class Workload:
             else:
                 t["warped"] = t["f2"]
             t["out"] = ops.correlation(t["f1"], t["warped"], *CORR_P)
+            self._record(lv, l, corr=t["out"], **({"warped": t["warped"]} if l > 0 else {}))
 
     def _levels_bwd(self, lv, levels, keep):
         ops = torch.ops.cerberus
@@ -183,9 +216,12 @@ class Workload:
             g1, g2 = ops.correlation_backward(t["f1"], t["warped"], t["gout"], *CORR_P)
             keep.append(g1)
             if l > 0:
-                keep += ops.flow_warp_backward_ctx(t["f2"], t["flow"], t["ctx"], g2, 1, 0, True, True)
+                gi, gf = ops.flow_warp_backward_ctx(t["f2"], t["flow"], t["ctx"], g2, 1, 0, True, True)
+                keep += [gi, gf]
+                self._record(lv, l, grad_f1=g1, grad_f2=gi, grad_flow=gf)
             else:
                 keep.append(g2)
+                self._record(lv, l, grad_f1=g1, grad_f2=g2)
 
     def step_hybrid(self, streams, ncoarse=2):
         """the two flow directions STACKED into one batched call per op on the `ncoarse` coarsest levels
@@ -197,6 +233,7 @@ class Workload:
             for a, b in zip(*self.dirs):
                 self.stacked.append({k: (torch.cat([a[k], b[k]], 0) if a[k] is not None else None)
                                      for k in ("f1", "f2", "gout", "flow")})
+            self.tags[id(self.stacked)] = "both"
         keep = []
         main = torch.cuda.current_stream()
         n = len(self.levels)
@@ -222,6 +259,7 @@ class Workload:
             for a, b in zip(*self.dirs):
                 self.stacked.append({k: (torch.cat([a[k], b[k]], 0) if a[k] is not None else None)
                                      for k in ("f1", "f2", "gout", "flow")})
+            self.tags[id(self.stacked)] = "both"
         keep = []
         main, side = torch.cuda.current_stream(), streams[0]
         forked = [False]
@@ -1344,11 +1382,57 @@ def model_step_mode(args, device, rank, world, dist, quiet=False):
     return result
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs writes at most this many bytes of array data in all
+
+
+def dump_indices(name, numel, count):
+    """The flat indices of the elements --dump-outputs keeps of an array: `count` of its `numel` drawn without
+    replacement by numpy's default_rng seeded with crc32(name), in increasing order -- the same in every run."""
+    import zlib
+    return np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(numel, count, replace=False))
+
+
+def dump_outputs(outputs, path):
+    """--dump-outputs: every tensor of `outputs` ({name: tensor}) as <path>/<name>.npy in float32.  A tensor larger
+    than its even share of DUMP_BYTES is written as the 1-D sample dump_indices() picks of its flattened elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // 4 // max(1, len(outputs))
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > share:
+            t = t.reshape(-1)[torch.from_numpy(dump_indices(name, t.numel(), share)).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
+def _default_steps(args, steps, warmup):
+    """--steps / --warmup not given: the defaults of the step being timed (one of them given: the other one keeps
+    the op step's default)."""
+    if args.steps is None and args.warmup is None:
+        args.steps, args.warmup = steps, warmup
+    args.steps = 200 if args.steps is None else args.steps
+    args.warmup = 20 if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 200 for the op step; --step model 20, --step head 30, --device cpu 3)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps right before the timed ones (default 20; --step model 3, --step head 5, "
+                         "--device cpu 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="the op step: after the headline also measure everything beside it -- the per-kernel, in-step "
+                         "and counter passes and the roofline they feed, the steady-state and after-idle passes, the "
+                         "stock-PyTorch GPU and CPU baselines and the extra configurations (extra.*).  Without it a run "
+                         "sets up, warms up, times the K steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="the op step: after the timed steps write what the last one computed -- per flow direction and "
+                         "level the correlation output, the warped image and the gradients of f1, f2 and the flow -- as "
+                         "DIR/<name>.npy in float32 (at most 48 MiB in all: larger arrays as a fixed, seeded sample of "
+                         "their elements); the inputs are the same in every run with the same arguments")
     ap.add_argument("--pairs", type=int, default=4, help="image pairs per GPU per step")
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--height", type=int, default=512)
@@ -1373,9 +1457,9 @@ def main():
     ap.add_argument("--chains", type=int, default=1,
                     help="split each direction's batch into this many independent sub-batches, "
                          "one HIP stream each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip torch_gpu_reference and cpu_baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the short side passes of the default line (extra.config5_f16, extra.bf16_1024x512, extra.flow_noise, "
+                    help="--full: skip the short side passes (extra.config5_f16, extra.bf16_1024x512, extra.flow_noise, "
                          "extra.ragged, extra.loss_side, extra.model_step)")
     ap.add_argument("--probe-steps", type=int, default=20)
     ap.add_argument("--flow", choices=["smooth", "noise"], default="smooth",
@@ -1413,14 +1497,14 @@ def main():
                     help="--step model at N = 1: after the timed region also time the step with the stock-PyTorch fallback ops and "
                          "under bf16 autocast (`backend_table`)")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold (HBM-resident inputs) per-kernel pass")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cold (HBM-resident inputs) per-kernel pass")
     ap.add_argument("--sync-bn", action="store_true",
                     help="--step model, N > 1: SyncBatchNorm instead of per-replica BatchNorm statistics")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="skip the two counter passes (FETCH_SIZE / WRITE_SIZE children) behind roofline.traffic; the committed "
+                    help="--full: skip the two counter passes (FETCH_SIZE / WRITE_SIZE children) behind roofline.traffic; the committed "
                          "figure of profiles/ is reported instead, labelled as such")
     ap.add_argument("--probe-after", action="store_true",
-                    help="run the per-kernel passes after the timed region (the order of rounds 1-3) instead of before it")
+                    help="--full: run the per-kernel passes after the timed region (the order of rounds 1-3) instead of before it")
     ap.add_argument("--bwd-variant", type=int, default=0, help="experiments: option corr_bwd_variant")
     ap.add_argument("--fwd-variant", type=int, default=0, help="experiments: option corr_fwd_variant")
     ap.add_argument("--bwd-cslice", type=int, default=0, help="experiments: option corr_bwd_cslice")
@@ -1443,6 +1527,8 @@ def main():
         # the N > 1 route on a box without GPUs: same launcher / rendezvous / DDP / timed region / gather, gloo instead of RCCL
         if (args.step or "model") != "model":
             raise SystemExit("--device cpu runs --step model only (the hot-path ops have no CPU implementation)")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the op step (--step ops) only")
         args.step = "model"
         device = torch.device("cpu")
         dist = None
@@ -1451,9 +1537,8 @@ def main():
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
             os.environ.setdefault("MASTER_PORT", "29511")
             dist.init_process_group("gloo", rank=rank, world_size=world)
-        if args.steps == 200 and args.warmup == 20:
-            args.steps, args.warmup = 3, 1
-        torch.set_num_threads(max(1, (os.cpu_count() or 1) // max(1, world)))
+        _default_steps(args, 3, 1)
+        torch.set_num_threads(max(1, usable_cores()[0] // max(1, world)))      # not os.cpu_count(): see usable_cores()
         model_step_mode(args, device, rank, world, dist)
         if dist is not None:
             dist.barrier()
@@ -1481,13 +1566,15 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)  # RCCL
 
     if args.trace_child:
+        _default_steps(args, 200, 20)
         trace_child(args, device)
         return
     if args.step is None:
         args.step = "model" if world > 1 else "ops"
+    if args.dump_outputs and args.step != "ops":
+        raise SystemExit("--dump-outputs writes the outputs of the op step (--step ops) only")
     if args.step == "model":
-        if args.steps == 200 and args.warmup == 20:      # the defaults are sized for the 0.4 ms op step
-            args.steps, args.warmup = 20, 3
+        _default_steps(args, 20, 3)      # the op step's defaults are sized for its 0.4 ms
         model_step_mode(args, device, rank, world, dist)
         if dist is not None:
             dist.barrier()
@@ -1498,14 +1585,14 @@ def main():
             raise SystemExit("--step head runs in fp32")
         if world > 1 and dist is None:
             raise SystemExit("--step head with N > 1 needs torch.distributed")
-        if args.steps == 200 and args.warmup == 20:      # the defaults are sized for the 0.4 ms op step
-            args.steps, args.warmup = 30, 5
+        _default_steps(args, 30, 5)      # the op step's defaults are sized for its 0.4 ms
         head_step_mode(args, device, rank, world, dist)
         if dist is not None:
             dist.barrier()
             dist.destroy_process_group()
         return
 
+    _default_steps(args, 200, 20)
     dtype = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
     wl = Workload(args.pairs, args.width, args.height, device, args.flow, args.fuse_directions,
                   args.chains, dtype)
@@ -1533,6 +1620,9 @@ def main():
         with torch.cuda.graph(graph):
             held = step_fn()  # noqa: F841  keep outputs alive for the graph's pool
     run = graph.replay if graph is not None else step_fn
+    # the tensors the captured step writes its results into (every replay rewrites them); eagerly, the last step's
+    # own tensors, taken after the timed region
+    step_results = dict(wl.results) if graph is not None else None
 
     # ---- per-kernel pass (rank 0 only): every launch of the step timed on its own ----
     # R back-to-back launches of ONE kernel are captured into a hipGraph (no host launch gaps between them) and
@@ -1541,9 +1631,9 @@ def main():
     # the line needs anyway, and with them in front the W warm-up steps and the K timed steps start on a chip
     # that is already at its working clock: with the driver's --steps 20 --warmup 5 (a 7 ms timed region) the
     # same build on the same box read 10.8 k pairs/s with the passes behind the timed region and 12.1 k at
-    # --steps 200 -- the first replays after seconds of host-side set-up ran at the idle clock.
+    # --steps 200 -- the first replays after seconds of host-side set-up ran at the idle clock.  Run with --full only.
     probe = None
-    if rank == 0 and not args.probe_after:
+    if rank == 0 and args.full and not args.probe_after:
         instep, instep_info = ((None, "skipped") if (args.no_cold or args.fuse_directions or args.chains > 1 or world > 1)
                                else in_step_times(args, len(wl.levels)))
         live, live_info = ((None, "skipped") if instep is None or args.no_traffic else live_traffic(args, len(wl.levels)))
@@ -1618,13 +1708,17 @@ def main():
         return dt
 
     use_exchange = exchange is not None and args.with_exchange and not args.no_exchange
+    if graph is None:
+        wl.results = {}      # eager: only what the timed steps record (the per-kernel pass records one direction)
     elapsed = timed(args.steps, use_exchange)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(step_results), args.dump_outputs)
     # Round-over-round comparability: rounds 1-3 timed the K steps right after seconds of
     # host-side set-up (the chip's post-idle transient inside the timed region); since round 4 the measurement passes and 80
     # replays of the steady-state pass come first.  The old-order figure is reproduced here, after the headline: 0.5 s of
     # idle, the same W warm-up replays, the same K timed steps.
     after_idle = None
-    if graph is not None and not args.probe_after:
+    if graph is not None and args.full and not args.probe_after:
         time.sleep(0.5)
         for _ in range(args.warmup):
             graph.replay()
@@ -1706,7 +1800,7 @@ def main():
             },
         }
         result.update(extra)
-        if steady is not None:
+        if steady is not None and (args.full or world > 1):
             result["steady_state"] = steady
         if world > 1 and steady is not None:
             # the like-for-like ratio at the top level of every N > 1 line: the ops have no collective, so the single-GPU
@@ -1716,11 +1810,13 @@ def main():
             result["scaling_efficiency"] = round(result["value"] / (world * steady_slowest), 4)
         # what preceded the timed region besides the W warm-up steps `warmup` reports
         result["pre_timed"] = {
-            "probe_order": "after" if args.probe_after else "before",
+            "probe_order": ("after" if args.probe_after else "before") if args.full else "not run (--full runs them)",
             "graph_replays_before_warmup": 0 if (args.probe_after or graph is None) else 80,
             "what": ("the per-kernel / in-step / counter passes (rank 0) and the 20 + 60 replays of the steady_state pass "
                      "(every rank) run BEFORE the W warm-up and K timed steps; rounds 1-3 ran the probes after the timed "
-                     "region (--probe-after): compare those rounds with first_steps_after_idle")}
+                     "region (--probe-after): compare those rounds with first_steps_after_idle") if args.full else
+                    ("20 + 60 untimed replays of the step graph (every rank) run BEFORE the W warm-up and K timed steps, "
+                     "so that these start on a chip in its working state")}
         if after_idle is not None:
             result["first_steps_after_idle"] = {
                 "value": round(pairs_total / after_idle, 2), "unit": "image-pairs/s",
@@ -1730,7 +1826,7 @@ def main():
                         "1-3 (what --probe-after measures as `value`); the chip's post-idle transient lies inside it"}
 
     # ---- the roofline report from the per-kernel passes ----
-    if rank == 0:
+    if rank == 0 and args.full:
         if probe is None:   # --probe-after: the round-3 order
             hot, cold = per_kernel_times(wl, max(2, args.probe_steps), cold=not args.no_cold)
             instep, instep_info = ((None, "skipped") if (args.no_cold or args.fuse_directions or args.chains > 1 or world > 1)
@@ -1891,6 +1987,7 @@ def main():
             except Exception as exc:
                 extra_lines["model_step"] = {"error": repr(exc)[:200]}
             result["extra"] = extra_lines
+    if rank == 0:
         print(json.dumps(result), flush=True)
 
     if dist is not None:

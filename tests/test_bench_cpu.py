@@ -121,7 +121,36 @@ def test_cpu_dry_run_refuses_the_op_only_step():
 
 def test_cpu_baseline_also_reports_the_all_cores_figure_as_specified():
     r = bench.cpu_baseline([(8, 8, 16), (4, 16, 32)], budget_s=5.0)
-    assert r["value_all_cores"] > 0 and r["cores_all"] == os.cpu_count()
+    assert r["value_all_cores"] > 0 and r["cores_all"] == bench.usable_cores()[0]        # os.cpu_count() where no quota applies
     assert set(r["all_cores"]["per_shape_ms"]) == {"L0", "L1"}
     pair_s = 2e-3 * sum(r["all_cores"]["per_shape_ms"]["L%d" % l]["fwd_bwd_ms_median"] for l in range(2))
     assert np.isclose(r["value_all_cores"], 1.0 / pair_s, rtol=1e-3)
+
+
+def test_dump_outputs_writes_float32_and_the_same_sample_every_time(tmp_path, monkeypatch):
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 1024)            # 1024 elements per array for two arrays
+    outs = {"small": torch.linspace(-1, 1, 12, dtype=torch.float16).reshape(3, 4),
+            "big": torch.arange(5000, dtype=torch.float32).reshape(50, 100)}
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, str(tmp_path / run))
+    small = np.load(str(tmp_path / "a" / "small.npy"))
+    assert small.dtype == np.float32 and small.shape == (3, 4)
+    assert np.array_equal(small, outs["small"].float().numpy())
+    big = np.load(str(tmp_path / "a" / "big.npy"))
+    assert big.dtype == np.float32 and big.shape == (1024,)
+    assert np.array_equal(big, bench.dump_indices("big", 5000, 1024).astype(np.float32))   # element i holds i
+    assert np.all(np.diff(big) > 0)                                                          # distinct, in order
+    for name in ("small", "big"):
+        assert np.array_equal(np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy"))))
+
+
+def test_workload_outputs_name_every_direction_and_level_and_split_stacked_launches():
+    import torch
+    wl = bench.Workload(2, 64, 32, torch.device("cpu"))
+    assert len(wl.dirs) == 2 and sorted(wl.tags.values()) == ["d0", "d1"]
+    both = torch.arange(4 * 3, dtype=torch.float32).reshape(4, 3)            # a launch carrying both directions (2 + 2)
+    wl.results = {("both", 0, "corr"): both, ("d1", 2, "grad_flow"): torch.ones(2, 2, 8, 16)}
+    out = wl.outputs()
+    assert sorted(out) == ["d0_L0_corr", "d1_L0_corr", "d1_L2_grad_flow"]
+    assert torch.equal(out["d0_L0_corr"], both[:2]) and torch.equal(out["d1_L0_corr"], both[2:])
