@@ -221,7 +221,7 @@ int cerberus_warp_correlation_forward(const void *input1, const void *input2, co
     const int rc = warp_args_ok(B, C, H, W, pad_mode, CERB_INTERP_BILINEAR, dtype);
     if (rc) return rc;
     if (!dtype_ok(flow_dtype)) return CERB_EDTYPE;
-    if (pad_mode == CERB_PAD_REFLECTION) return CERB_EUNSUPPORTED;   // (no reference caller; the training path could not differentiate it)
+    if (pad_mode == CERB_PAD_REFLECTION) return CERB_EUNSUPPORTED;   // (no reference caller; not built into the fused kernel)
     if (B == 0) return CERB_OK;
     if (!input1 || !input2 || !flow || !output) return CERB_EINVAL;
     if (out_batch_stride != 0 && out_batch_stride < static_cast<int64_t>(81) * H * W) return CERB_EINVAL;

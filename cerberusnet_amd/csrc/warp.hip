@@ -56,6 +56,12 @@ __global__ __launch_bounds__(kPix * kCg) void warp_fwd_kernel(
         const T *img = image + static_cast<int64_t>(b) * C * plane;
         T *dst = out + static_cast<int64_t>(b) * C * plane + p;
         if (interp == CERB_INTERP_NEAREST) {
+            if (ctx && cg == 0) {   // the backward's context: positions and the floor taps' ranges (the snapped tap is one of them)
+                float *pos = ctx_pos(ctx, B, H, W) + static_cast<int64_t>(b) * 2 * plane + p;
+                pos[0] = static_cast<float>(cx.pos);
+                pos[plane] = static_cast<float>(cy.pos);
+                range.add(x, y, tap_index(static_cast<float>(floor(cx.pos))), tap_index(static_cast<float>(floor(cy.pos))), W, H);
+            }
             const A xn = nearbyint(cx.pos), yn = nearbyint(cy.pos);
             const bool ok = xn >= A(0) && xn < static_cast<A>(W) && yn >= A(0) && yn < static_cast<A>(H);
             const int64_t off = ok ? static_cast<int64_t>(yn) * W + static_cast<int64_t>(xn) : 0;
@@ -284,7 +290,7 @@ __device__ __forceinline__ void atomic_accumulate(hip_bfloat16 *p, float v) { at
 template <typename T, typename F, bool PAIR, int kCg>
 __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
     const T *__restrict__ image, const F *__restrict__ flow, const T *__restrict__ gout,
-    T *__restrict__ gimage, F *__restrict__ gflow, int B, int C, int H, int W, int pad_mode) {
+    T *__restrict__ gimage, F *__restrict__ gflow, int B, int C, int H, int W, int pad_mode, int interp) {
     using A = typename Acc<T>::type;
     __shared__ A part[kCg][2][kPix];
     const int64_t plane = static_cast<int64_t>(H) * W;
@@ -311,9 +317,18 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
         const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
         const int64_t o00 = static_cast<int64_t>(y0) * W + x0;
         const int64_t base = static_cast<int64_t>(b) * C * plane;
+        if (interp == CERB_INTERP_NEAREST) {
+            // grad_image: gradOutput added to the nearbyint tap (ATen's scatter); grad_flow: zero, stored below
+            const A xn = nearbyint(cx.pos), yn = nearbyint(cy.pos);
+            const bool ok = xn >= A(0) && xn < static_cast<A>(W) && yn >= A(0) && yn < static_cast<A>(H);
+            if (gimage && ok) {
+                const int64_t q = base + static_cast<int64_t>(yn) * W + static_cast<int64_t>(xn);
+                for (int c = cg; c < C; c += kCg) atomic_accumulate(gimage + q + c * plane, ld(gout + base + c * plane + p));
+            }
+        }
         // kU channels per trip: all loads of a trip are issued before any is consumed
         constexpr int kU = 4;
-        for (int c = cg; c < C; c += kU * kCg) {
+        for (int c = cg; c < C && interp != CERB_INTERP_NEAREST; c += kU * kCg) {
             A g[kU], vnw[kU], vne[kU], vsw[kU], vse[kU];
 #pragma unroll
             for (int u = 0; u < kU; ++u) {
@@ -355,8 +370,9 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
         for (int k = 0; k < kCg; ++k) { sx += part[k][0][lane]; sy += part[k][1][lane]; }
         // autograd order: grad_grid = mult * sum ; through norm_grid: / (size-1) then * 2.0
         F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
-        st(gf, cx.mult * sx / static_cast<A>(W - 1) * A(2.0));
-        st(gf + plane, cy.mult * sy / static_cast<A>(H - 1) * A(2.0));
+        const bool nearest = interp == CERB_INTERP_NEAREST;   // no gradient by the position: exact zeros
+        st(gf, nearest ? A(0) : cx.mult * sx / static_cast<A>(W - 1) * A(2.0));
+        st(gf + plane, nearest ? A(0) : cy.mult * sy / static_cast<A>(H - 1) * A(2.0));
     }
 }
 
@@ -389,7 +405,7 @@ template <typename T, typename F, int NC, int PX, bool BWD>
 __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ image, const F *__restrict__ flow,
                                                         const T *__restrict__ gout, T *__restrict__ out,
                                                         F *__restrict__ gflow, int items, int segs, int H, int W,
-                                                        int pad_mode) {
+                                                        int pad_mode, int interp) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int esz = sizeof(T), fsz = sizeof(F);
     const int plane = H * W;            // the launcher guarantees 4 * plane * 4 < 2^31
@@ -401,6 +417,18 @@ __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ im
     const __amdgpu_buffer_rsrc_t r_img = uniform_rsrc(image + static_cast<int64_t>(b) * NC * plane, NC * plane * esz);
     const __amdgpu_buffer_rsrc_t r_flow = uniform_rsrc(flow + static_cast<int64_t>(b) * 2 * plane, 2 * plane * fsz);
     const __amdgpu_buffer_rsrc_t r_go = uniform_rsrc(BWD ? gout + static_cast<int64_t>(b) * NC * plane : image, NC * plane * esz);
+    if (BWD && interp == CERB_INTERP_NEAREST) {
+        // nearest: grad_flow is exactly zero (the op allocates it uninitialised)
+        const __amdgpu_buffer_rsrc_t r_gf = uniform_rsrc(gflow + static_cast<int64_t>(b) * 2 * plane, 2 * plane * fsz);
+#pragma unroll
+        for (int i = 0; i < PX; ++i) {
+            const int xz = sg * (PX * kPix) + i * kPix + lane;
+            const int pz = xz < W ? y * W + xz : kDeadOffset / 4;
+            buffer_store_px<F>(r_gf, pz * fsz, 0, 0.f);
+            buffer_store_px<F>(r_gf, pz * fsz, plane * fsz, 0.f);
+        }
+        return;
+    }
     float fx[PX], fy[PX], g[NC][PX];
     int pix[PX], xs[PX];
 #pragma unroll
@@ -532,8 +560,8 @@ __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ im
 template <typename T, typename F>
 __device__ __forceinline__ bool flow_role_staged(
     float *__restrict__ win, int cap, int4 *__restrict__ boxes, const T *__restrict__ image,
-    const T *__restrict__ gout, const void *__restrict__ ctx, F *__restrict__ gflow, int flow_block,
-    int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
+    const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow, F *__restrict__ gflow,
+    int flow_block, int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int esz = sizeof(T);
     constexpr int SR = kStageRows, NPL = 4;   // strips per workgroup, partial sums per lane
@@ -599,11 +627,8 @@ __device__ __forceinline__ bool flow_role_staged(
 #pragma unroll
     for (int k = 0; k < 4; ++k) { sx += gix[k]; sy += giy[k]; }
     if (live) {
-        float mx = static_cast<float>(W) / 2.0f, my = static_cast<float>(H) / 2.0f;
-        if (pad_mode == CERB_PAD_BORDER) {
-            if (ixp <= 0.f || ixp >= static_cast<float>(W - 1)) mx = 0.f;
-            if (iyp <= 0.f || iyp >= static_cast<float>(H - 1)) my = 0.f;
-        }
+        const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + p;
+        const float mx = ctx_grad_mult(ixp, x, fl, W, pad_mode), my = ctx_grad_mult(iyp, y, fl + plane, H, pad_mode);
         F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
         st(gf, mx * sx / static_cast<float>(W - 1) * 2.0f);
         st(gf + plane, my * sy / static_cast<float>(H - 1) * 2.0f);
@@ -618,7 +643,7 @@ __device__ __forceinline__ bool flow_role_staged(
 // channels, eight in flight; channel c adds into partial c & 3, the partials are summed 0..3 (the order of every role).
 template <typename T, typename F>
 __device__ __forceinline__ void flow_pixel_direct(
-    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx,
+    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow,
     F *__restrict__ gflow, int b, int p, int B, int C, int H, int W, int pad_mode) {
     const int plane = H * W;
     const float *pos = ctx_pos(ctx, B, H, W) + static_cast<int64_t>(b) * 2 * plane;
@@ -651,11 +676,8 @@ __device__ __forceinline__ void flow_pixel_direct(
     float sx = 0.f, sy = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { sx += gix[k]; sy += giy[k]; }
-    float mx = static_cast<float>(W) / 2.0f, my = static_cast<float>(H) / 2.0f;
-    if (pad_mode == CERB_PAD_BORDER) {
-        if (ixp <= 0.f || ixp >= static_cast<float>(W - 1)) mx = 0.f;
-        if (iyp <= 0.f || iyp >= static_cast<float>(H - 1)) my = 0.f;
-    }
+    const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + p;
+    const float mx = ctx_grad_mult(ixp, p % W, fl, W, pad_mode), my = ctx_grad_mult(iyp, p / W, fl + plane, H, pad_mode);
     F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
     st(gf, mx * sx / static_cast<float>(W - 1) * 2.0f);
     st(gf + plane, my * sy / static_cast<float>(H - 1) * 2.0f);
@@ -664,7 +686,7 @@ __device__ __forceinline__ void flow_pixel_direct(
 // The 8 x 32 tile of flow_role_staged by direct gathers: one wave per strip
 template <typename T, typename F>
 __device__ __forceinline__ void flow_role_tile_direct(
-    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx,
+    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow,
     F *__restrict__ gflow, int flow_block, int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
     const int lane = threadIdx.x & (kPix - 1), wave = threadIdx.x / kPix;
     constexpr int SR = kStageRows;
@@ -677,13 +699,13 @@ __device__ __forceinline__ void flow_role_tile_direct(
     const int jy = ty * SR + wave;
     int x = 0, y = 0;
     if (!(jy < strips.ny && strips.pixel(jy * strips.nx + tx, lane, H, W, x, y))) return;
-    flow_pixel_direct<T, F>(image, gout, ctx, gflow, b, y * W + x, B, C, H, W, pad_mode);
+    flow_pixel_direct<T, F>(image, gout, ctx, flow, gflow, b, y * W + x, B, C, H, W, pad_mode);
 }
 
 // The 8 x 64 tile of flow_role16 (16-bit storage) by direct gathers: a lane's two pixels one after the other
 template <typename T, typename F>
 __device__ __forceinline__ void flow_role16_direct(
-    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx,
+    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow,
     F *__restrict__ gflow, int flow_block, int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
     const int lane = threadIdx.x & (kPix - 1), wave = threadIdx.x / kPix;
     const int ntx = (W + kTile16W - 1) / kTile16W, nty = (H + kTile16H - 1) / kTile16H;
@@ -693,8 +715,8 @@ __device__ __forceinline__ void flow_role16_direct(
     const int b = id / nty;
     const int y = ty * kTile16H + wave * 2 + (lane >> 5), xa = tx * kTile16W + 2 * (lane & 31);
     if (!(y < H && xa < W)) return;
-    flow_pixel_direct<T, F>(image, gout, ctx, gflow, b, y * W + xa, B, C, H, W, pad_mode);
-    if (xa + 1 < W) flow_pixel_direct<T, F>(image, gout, ctx, gflow, b, y * W + xa + 1, B, C, H, W, pad_mode);
+    flow_pixel_direct<T, F>(image, gout, ctx, flow, gflow, b, y * W + xa, B, C, H, W, pad_mode);
+    if (xa + 1 < W) flow_pixel_direct<T, F>(image, gout, ctx, flow, gflow, b, y * W + xa + 1, B, C, H, W, pad_mode);
 }
 
 #ifdef CERB_STAMP
@@ -721,12 +743,16 @@ template <int TH> struct TileGeom {
 #ifndef CERB_TILE16_WPS
 #define CERB_TILE16_WPS 4
 #endif
-template <typename T, typename F, int TH, int CW, int NS, int PR = 0>
+// REFL: the reflection pad's instantiation -- its flow roles recompute the multiplier's sign from the flow; kept out of the
+// border / zeros kernels, where that code costs the 16-bit forms (at their 128 VGPRs) two more spilled registers
+template <typename T, typename F, int TH, int CW, int NS, int PR = 0, bool REFL = false>
 __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_tile_kernel(
-    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx,
+    const T *__restrict__ image, const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow,
     T *__restrict__ gimage, F *__restrict__ gflow, int B, int C, int H, int W,
-    int tiles_x, int tiles_y, int nrange, int crange, int ntile_blocks, int pad_mode,
+    int tiles_x, int tiles_y, int nrange, int crange, int ntile_blocks, int pad_arg, int interp,
     int flow_staged, int flow_sub, int stagger) {
+    // (a pad mode the compiler can see is not reflection unless REFL)
+    const int pad_mode = REFL ? CERB_PAD_REFLECTION : pad_arg == CERB_PAD_BORDER ? CERB_PAD_BORDER : CERB_PAD_ZEROS;
     constexpr int TW = kTileW, PW = TileGeom<TH>::PW, PS = TileGeom<TH>::PS;
     constexpr int NP = CW / 2;                       // channel pairs = planes of 64-bit slots
     static_assert(CW % 2 == 0, "channels are accumulated in pairs");
@@ -748,8 +774,8 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
                 // 16-bit storage: an 8 x 64 tile, two pixels per lane, the raw 16-bit window by LDS-DMA (warp16_common.h)
                 const int fb = blockIdx.x - ntile_blocks, nfb = gridDim.x - ntile_blocks;
                 if (!flow_role16<T, F>(reinterpret_cast<char *>(acc), NP * PS * 8, reinterpret_cast<int4 *>(&red[0][0]), image,
-                                       gout, ctx, gflow, fb, nfb, B, C, H, W, pad_mode))
-                    flow_role16_direct<T, F>(image, gout, ctx, gflow, fb, nfb, B, C, H, W, pad_mode);
+                                       gout, ctx, flow, gflow, fb, nfb, B, C, H, W, pad_mode))
+                    flow_role16_direct<T, F>(image, gout, ctx, flow, gflow, fb, nfb, B, C, H, W, pad_mode);
                 return;
             }
         }
@@ -757,9 +783,9 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
             // an 8 x 32 tile x all channels through an LDS window (the accumulators' LDS)
             const int fb = blockIdx.x - ntile_blocks, nfb = gridDim.x - ntile_blocks;
             if (!flow_role_staged<T, F>(reinterpret_cast<float *>(acc), NP * PS * 2,
-                                        reinterpret_cast<int4 *>(&red[0][0]), image, gout, ctx, gflow,
+                                        reinterpret_cast<int4 *>(&red[0][0]), image, gout, ctx, flow, gflow,
                                         fb, nfb, B, C, H, W, pad_mode))
-                flow_role_tile_direct<T, F>(image, gout, ctx, gflow, fb, nfb, B, C, H, W, pad_mode);
+                flow_role_tile_direct<T, F>(image, gout, ctx, flow, gflow, fb, nfb, B, C, H, W, pad_mode);
             return;
         }
         // one strip of 64 pixels x 4 channel groups (one wave each); positions from the context.
@@ -780,6 +806,15 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
         int x, y;
         const bool live = strips.pixel(strip % spp, slane, H, W, x, y);
         const int p = y * W + x;
+        if (interp == CERB_INTERP_NEAREST) {
+            // nearest: no gradient by the position -- exact zeros (the launcher gives nearest this role with flow_sub = 1)
+            if (wave == 0 && live) {
+                F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
+                st(gf, 0.f);
+                st(gf + plane, 0.f);
+            }
+            return;
+        }
         const int pc = live ? p : 0;
         const float *pos = ctx_pos(ctx, B, H, W) + static_cast<int64_t>(b) * 2 * plane;
         const float ixp = pos[pc], iyp = pos[plane + pc];
@@ -821,13 +856,10 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
             for (int q = 0; q < flow_sub; ++q)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { sx += part[k][0][q * npx + lane]; sy += part[k][1][q * npx + lane]; }
-            // clip_coordinates_set_grad from the clamped position, then autograd's order:
+            // the pad mode's multiplier, then autograd's order:
             // grad_grid = mult * sum ; through norm_grid: / (size-1) then * 2.0
-            float mx = static_cast<float>(W) / 2.0f, my = static_cast<float>(H) / 2.0f;
-            if (pad_mode == CERB_PAD_BORDER) {
-                if (ixp <= 0.f || ixp >= static_cast<float>(W - 1)) mx = 0.f;
-                if (iyp <= 0.f || iyp >= static_cast<float>(H - 1)) my = 0.f;
-            }
+            const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + p;
+            const float mx = ctx_grad_mult(ixp, x, fl, W, pad_mode), my = ctx_grad_mult(iyp, y, fl + plane, H, pad_mode);
             F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
             st(gf, mx * sx / static_cast<float>(W - 1) * 2.0f);
             st(gf + plane, my * sy / static_cast<float>(H - 1) * 2.0f);
@@ -951,8 +983,8 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
         const int lx = tap_index(x0f) - tx0 + 1, ly = tap_index(y0f) - ty0 + 1;
         const bool in = on && lx >= 0 && lx <= TW && ly >= 0 && ly <= TH;
         s.o = in ? ly * PW + lx : -1;
-        s.fx = ixj - x0f;
-        s.fy = iyj - y0f;
+        s.fx = tap_fraction(ixj, x0f, interp);
+        s.fy = tap_fraction(iyj, y0f, interp);
         return in;
     };
     // walks idx = tid + 256 k over the region as (row, column) without divisions
@@ -1070,6 +1102,11 @@ __global__ __launch_bounds__(256, TH == 16 ? CERB_TILE16_WPS : 4) void warp_bwd_
             for (int c = 0; c < CW; ++c) {
                 if (c >= cw) break;
                 float *f = reinterpret_cast<float *>(a + (c / 2) * PS) + (c & 1);
+                if (interp == CERB_INTERP_NEAREST) {
+                    // only the snapped tap: 0 * NaN must not reach the three others (ATen adds to one tap)
+                    atomicAdd(f + (s.fy != 0.f ? 2 * PW : 0) + (s.fx != 0.f ? 2 : 0), g[c]);
+                    continue;
+                }
                 atomicAdd(f, w00 * g[c]);
                 atomicAdd(f + 2, w01 * g[c]);
                 atomicAdd(f + 2 * PW, w10 * g[c]);
@@ -1420,7 +1457,7 @@ size_t dtype_size(int dtype) {
 // the few-channel kernels; CERB_EUNSUPPORTED when they do not apply (C > 4, fp64, or a batch item beyond 32-bit offsets)
 template <bool BWD>
 static int launch_fewc(const void *image, const void *flow, const void *gout, void *out, void *gflow, int B, int C, int H,
-                       int W, int pad_mode, int dtype, int flow_dtype, hipStream_t s) {
+                       int W, int pad_mode, int interp, int dtype, int flow_dtype, hipStream_t s) {
     const int64_t plane = static_cast<int64_t>(H) * W;
     if (C > 4 || dtype == CERB_F64 || plane * 16 >= (1ll << 31)) return CERB_EUNSUPPORTED;
     // four pixels per lane once a row has them and the launch is large (>= 2 workgroups per CU either way), else one
@@ -1434,7 +1471,7 @@ static int launch_fewc(const void *image, const void *flow, const void *gout, vo
     CERB_DISPATCH2(dtype, flow_dtype, if constexpr (!std::is_same<T, double>::value)                              \
         hipLaunchKernelGGL((warp_fewc_kernel<T, F, NC, PX, BWD>), grid, dim3(256), 0, s,                          \
         static_cast<const T *>(image), static_cast<const F *>(flow), static_cast<const T *>(gout),               \
-        static_cast<T *>(out), static_cast<F *>(gflow), static_cast<int>(items), segs, H, W, pad_mode))
+        static_cast<T *>(out), static_cast<F *>(gflow), static_cast<int>(items), segs, H, W, pad_mode, interp))
 #define CERB_FEWC_PX(NC) if (px4) { CERB_FEWC(NC, 4) } else { CERB_FEWC(NC, 1) }
     switch (C) {
         case 1: CERB_FEWC_PX(1) break;
@@ -1483,7 +1520,7 @@ int warp_forward(const void *image, const void *flow, void *out, void *ctx, int6
     if (nstrips > 0x7fffffff) return CERB_ETOOLARGE;
     if (!ctx && C <= 4 && interp == CERB_INTERP_BILINEAR && option(OPT_WARP_FEWC) >= 0) {
         // no context wanted and <= 4 channels (the loss's RGB warps): a lane owns its pixels with all their channels
-        const int rc = launch_fewc<false>(image, flow, nullptr, out, nullptr, B, C, H, W, pad_mode, dtype, flow_dtype, s);
+        const int rc = launch_fewc<false>(image, flow, nullptr, out, nullptr, B, C, H, W, pad_mode, interp, dtype, flow_dtype, s);
         if (rc != CERB_EUNSUPPORTED) return rc;
     }
     const int staged_opt = option(OPT_WARP_STAGED);
@@ -1536,8 +1573,8 @@ int warp_forward(const void *image, const void *flow, void *out, void *ctx, int6
 }
 
 template <typename T, typename F, int TH, int NS>
-static int launch_tiles(const void *image, const void *gout, const void *ctx, void *gimage,
-                        void *gflow, int B, int C, int H, int W, int pad_mode, hipStream_t s) {
+static int launch_tiles(const void *image, const void *flow, const void *gout, const void *ctx, void *gimage,
+                        void *gflow, int B, int C, int H, int W, int pad_mode, int interp, hipStream_t s) {
     constexpr int CW = 8;
     const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + TH - 1) / TH;
     const int64_t tiles = static_cast<int64_t>(B) * tiles_x * tiles_y;
@@ -1559,8 +1596,10 @@ static int launch_tiles(const void *image, const void *gout, const void *ctx, vo
     // strip role on a deep level (few pixels, many channels): quarter strips x 16 channel groups.  The choice
     // looks at one image only: an item's grad_flow must not depend on the batch it travels in (the summation
     // order differs from the four-group order the staged role shares with the plain strip role)
-    const int flow_sub = (C >= 64 && strips.per_image() <= 32 && staged_opt < 4) ? 4 : 1;
-    const bool flow_staged = gflow && W % 4 == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0 &&
+    // nearest: grad_flow is all zeros, stored by the plain strip role without a single load
+    const bool nearest = interp == CERB_INTERP_NEAREST;
+    const int flow_sub = (C >= 64 && strips.per_image() <= 32 && staged_opt < 4 && !nearest) ? 4 : 1;
+    const bool flow_staged = gflow && !nearest && W % 4 == 0 && (reinterpret_cast<uintptr_t>(image) & 15) == 0 &&
                              static_cast<int64_t>(C) * H * W * 4 < 0x7fffffff && staged_opt != 2 && flow_sub == 1 &&
                              (flow_tiles >= 512 || staged_opt >= 4);
     const int64_t nstrips = static_cast<int64_t>(B) * strips.per_image();
@@ -1589,18 +1628,20 @@ static int launch_tiles(const void *image, const void *gout, const void *ctx, vo
     // 16-bit storage: the tile role takes its sources as horizontally adjacent pairs (one dword of gradOutput per pair)
     constexpr bool can_pair = sizeof(T) == 2 && NS % 2 == 0;
     const bool pair_sources = can_pair && W % 2 == 0 && (reinterpret_cast<uintptr_t>(gout) & 3) == 0 && option(OPT_WARP_PAIR16) >= 0;
-#define CERB_LAUNCH_TILES(PR)                                                                          \
-    hipLaunchKernelGGL((warp_bwd_tile_kernel<T, F, TH, CW, NS, PR>),                                   \
+#define CERB_LAUNCH_TILES(PR, REFL)                                                                    \
+    hipLaunchKernelGGL((warp_bwd_tile_kernel<T, F, TH, CW, NS, PR, REFL>),                             \
                        dim3(static_cast<unsigned>(tile_blocks + flow_blocks)), dim3(256), 0, s,        \
                        static_cast<const T *>(image), static_cast<const T *>(gout), ctx,               \
-                       static_cast<T *>(gimage), static_cast<F *>(gflow), B,                           \
-                       C, H, W, tiles_x, tiles_y, nrange, crange, static_cast<int>(tile_blocks),       \
-                       pad_mode, flow16 ? 2 : flow_staged ? 1 : 0, flow_sub, stagger)
+                       static_cast<const F *>(flow), static_cast<T *>(gimage), static_cast<F *>(gflow), \
+                       B, C, H, W, tiles_x, tiles_y, nrange, crange, static_cast<int>(tile_blocks),    \
+                       pad_mode, interp, flow16 ? 2 : flow_staged ? 1 : 0, flow_sub, stagger)
+    const bool refl = pad_mode == CERB_PAD_REFLECTION;
     if constexpr (can_pair) {
-        if (pair_sources) CERB_LAUNCH_TILES(1); else CERB_LAUNCH_TILES(0);
+        if (pair_sources) { if (refl) CERB_LAUNCH_TILES(1, true); else CERB_LAUNCH_TILES(1, false); }
+        else { if (refl) CERB_LAUNCH_TILES(0, true); else CERB_LAUNCH_TILES(0, false); }
     } else {
         (void)pair_sources;
-        CERB_LAUNCH_TILES(0);
+        if (refl) CERB_LAUNCH_TILES(0, true); else CERB_LAUNCH_TILES(0, false);
     }
 #undef CERB_LAUNCH_TILES
     return launch_status();
@@ -1615,11 +1656,6 @@ int warp_backward(const void *image, const void *flow, const void *gout, void *g
     const size_t esz = dtype_size(dtype);
     if (!esz) return CERB_EDTYPE;
     if (!flow_dtype_ok(dtype, flow_dtype)) return CERB_EDTYPE;
-    if (interp == CERB_INTERP_NEAREST || pad_mode == CERB_PAD_REFLECTION) {
-        // nearest: grad_flow is identically zero and grad_image is a pure scatter;
-        // no reference caller differentiates through either.
-        return CERB_EUNSUPPORTED;
-    }
     if (ctx && (ctx_size < ctx_bytes(B, H, W) || (reinterpret_cast<uintptr_t>(ctx) & 15)))
         return CERB_EINVAL;
     const dim3 grid(static_cast<unsigned>((plane + kPix - 1) / kPix), B);
@@ -1657,16 +1693,16 @@ int warp_backward(const void *image, const void *flow, const void *gout, void *g
         if (th8) {
             // (16-bit storage: six sources per thread instead of five, an even number: they are taken as pairs)
             CERB_DISPATCH2(dtype, flow_dtype, if constexpr (!std::is_same<T, double>::value)
-                return (launch_tiles<T, F, 8, sizeof(T) == 2 ? 6 : 5>(image, gout, ctx, gimage, gflow, B, C, H, W, pad_mode, s)))
+                return (launch_tiles<T, F, 8, sizeof(T) == 2 ? 6 : 5>(image, flow, gout, ctx, gimage, gflow, B, C, H, W, pad_mode, interp, s)))
         } else {
             CERB_DISPATCH2(dtype, flow_dtype, if constexpr (!std::is_same<T, double>::value)
-                return (launch_tiles<T, F, 16, 6>(image, gout, ctx, gimage, gflow, B, C, H, W, pad_mode, s)))
+                return (launch_tiles<T, F, 16, 6>(image, flow, gout, ctx, gimage, gflow, B, C, H, W, pad_mode, interp, s)))
         }
         return CERB_EDTYPE;
     }
     if (!gimage && gflow && C <= 4 && option(OPT_WARP_FEWC) >= 0) {
         // grad_flow alone for <= 4 channels (the loss's RGB warps: the target image carries no gradient)
-        const int rc = launch_fewc<true>(image, flow, gout, nullptr, gflow, B, C, H, W, pad_mode, dtype, flow_dtype, s);
+        const int rc = launch_fewc<true>(image, flow, gout, nullptr, gflow, B, C, H, W, pad_mode, interp, dtype, flow_dtype, s);
         if (rc != CERB_EUNSUPPORTED) return rc;
     }
     if (gimage) {
@@ -1678,13 +1714,13 @@ int warp_backward(const void *image, const void *flow, const void *gout, void *g
             (warp_bwd_kernel<T, F, true, CG>), grid, dim3(kPix * CG), 0, s,
             static_cast<const T *>(image), static_cast<const F *>(flow),
             static_cast<const T *>(gout), static_cast<T *>(gimage), static_cast<F *>(gflow), B, C,
-            H, W, pad_mode)))
+            H, W, pad_mode, interp)))
     } else {
         CERB_PICK_CG(C, CERB_DISPATCH2(dtype, flow_dtype, hipLaunchKernelGGL(
             (warp_bwd_kernel<T, F, false, CG>), grid, dim3(kPix * CG), 0, s,
             static_cast<const T *>(image), static_cast<const F *>(flow),
             static_cast<const T *>(gout), static_cast<T *>(gimage), static_cast<F *>(gflow), B, C,
-            H, W, pad_mode)))
+            H, W, pad_mode, interp)))
     }
     return launch_status();
 }

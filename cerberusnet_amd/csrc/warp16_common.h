@@ -176,8 +176,8 @@ struct DmaPlan {
 template <typename T, typename F>
 __device__ __forceinline__ bool flow_role16(
     char *__restrict__ lds, int lds_bytes, int4 *__restrict__ boxes, const T *__restrict__ image,
-    const T *__restrict__ gout, const void *__restrict__ ctx, F *__restrict__ gflow, int flow_block,
-    int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
+    const T *__restrict__ gout, const void *__restrict__ ctx, const F *__restrict__ flow, F *__restrict__ gflow,
+    int flow_block, int nflow_blocks, int B, int C, int H, int W, int pad_mode) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int plane = H * W;
     const int tid = threadIdx.x;
@@ -283,13 +283,11 @@ __device__ __forceinline__ bool flow_role16(
     for (int k = 0; k < 4; ++k) { sx += gix[k]; sy += giy[k]; }
     if (live) {
         float mx[2], my[2];
+        const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + p;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            mx[k] = static_cast<float>(W) / 2.0f; my[k] = static_cast<float>(H) / 2.0f;
-            if (pad_mode == CERB_PAD_BORDER) {
-                if (ix[k] <= 0.f || ix[k] >= static_cast<float>(W - 1)) mx[k] = 0.f;
-                if (iy[k] <= 0.f || iy[k] >= static_cast<float>(H - 1)) my[k] = 0.f;
-            }
+            mx[k] = ctx_grad_mult(ix[k], xa + k, fl + k, W, pad_mode);
+            my[k] = ctx_grad_mult(iy[k], y, fl + plane + k, H, pad_mode);
         }
         // autograd order: grad_grid = mult * sum ; through norm_grid: / (size-1) then * 2.0
         const float rx0 = mx[0] * sx.x / static_cast<float>(W - 1) * 2.0f, rx1 = mx[1] * sx.y / static_cast<float>(W - 1) * 2.0f;

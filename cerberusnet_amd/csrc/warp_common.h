@@ -38,8 +38,9 @@ template <typename A> struct Coord {
 };
 
 #pragma clang fp contract(off)
+// The source index before padding: the reference's norm_grid, then ATen's unnormalise
 template <typename A>
-__device__ __forceinline__ Coord<A> source_coord(int pix, A flow, int size, int pad_mode) {
+__device__ __forceinline__ A unnormalized_coord(int pix, A flow, int size) {
     // norm_grid: 2.0 * v / (size - 1) - 1.0   (UnFlowLoss.py:30-31)
     const A v = static_cast<A>(pix) + flow;
     const A t = A(2.0) * v;
@@ -50,25 +51,70 @@ __device__ __forceinline__ Coord<A> source_coord(int pix, A flow, int size, int 
     // -ffp-contract on the vectorised CPU kernel: verified against torch CPU, 1-ulp
     // coordinate differences otherwise), so this one product is an explicit fma while
     // everything around it stays uncontracted.
-    A p = fma(g + A(1.0), static_cast<A>(size), A(-1.0)) / A(2.0);
+    return fma(g + A(1.0), static_cast<A>(size), A(-1.0)) / A(2.0);
+}
+
+// The sign of reflect_coordinates_set_grad(p, -1, 2*size-1) (min -0.5, span size): -1 left of
+// the low edge, flipped again on an odd number of spans.  True: the gradient is negated.
+template <typename A>
+__device__ __forceinline__ bool reflection_negates(A p, int size) {
+    const A d = p - A(-0.5);
+    const long long flips = static_cast<long long>(floor(fabs(d) / static_cast<A>(size)));
+    return (d < A(0)) == (flips % 2 == 0);
+}
+
+// clip_coordinates_set_grad: the gradient is 0 AT and beyond both limits
+template <typename A>
+__device__ __forceinline__ bool clip_kills_grad(A p, int size) {
+    return p <= A(0) || p >= static_cast<A>(size - 1);
+}
+
+template <typename A>
+__device__ __forceinline__ Coord<A> source_coord(int pix, A flow, int size, int pad_mode) {
+    A p = unnormalized_coord<A>(pix, flow, size);
     // d(p)/d(flow) = (size/2) * (1/(size-1)) * 2, in autograd's order
     A m = static_cast<A>(size) / A(2.0);
     if (pad_mode == CERB_PAD_BORDER) {
-        // clip_coordinates_set_grad: gradient is 0 AT and beyond both limits
         const A hi = static_cast<A>(size - 1);
-        if (p <= A(0)) { p = A(0); m = A(0); }
-        else if (p >= hi) { p = hi; m = A(0); }
+        if (clip_kills_grad(p, size)) m = A(0);
+        p = p <= A(0) ? A(0) : (p >= hi ? hi : p);
     } else if (pad_mode == CERB_PAD_REFLECTION) {
-        // reflect_coordinates(p, -1, 2*size-1) then clip (forward only)
+        // reflect_coordinates_set_grad(p, -1, 2*size-1) then clip_coordinates_set_grad:
+        // m * grad_refl * grad_clip
+        if (reflection_negates(p, size)) m = -m;
         const A mn = A(-0.5), span = static_cast<A>(size);
         A a = fabs(p - mn);
         A extra = fmod(a, span);
         const long long flips = static_cast<long long>(floor(a / span));
         p = (flips % 2 == 0) ? extra + mn : span - extra + mn;
+        if (clip_kills_grad(p, size)) m = A(0);
         const A hi = static_cast<A>(size - 1);
         p = p < A(0) ? A(0) : (p > hi ? hi : p);
     }
     return {p, m};
+}
+
+// d(pos)/d(flow component) of a position read back from a backward context: the multiplier of
+// every grad_flow role of the tiled backward -- the rule of source_coord, whose own multiplier
+// warp_bwd_kernel and the few-channel kernel take.  Border and reflection: 0 where the clipped
+// position sits on a limit.  Reflection: the context does not carry the reflection's sign, so it
+// is recomputed from the flow (`fl`: pixel `pix`'s flow component, read only here).
+template <typename F>
+__device__ __forceinline__ float ctx_grad_mult(float pos, int pix, const F *fl, int size, int pad_mode) {
+    float m = static_cast<float>(size) / 2.0f;
+    if (pad_mode != CERB_PAD_ZEROS && clip_kills_grad(pos, size)) return 0.f;
+    if (pad_mode == CERB_PAD_REFLECTION &&
+        reflection_negates(unnormalized_coord<float>(pix, static_cast<float>(ld(fl)), size), size))
+        m = -m;
+    return m;
+}
+
+// The tap fractions of a position for the owner-computes grad_image tile: (pos - floor(pos)) for
+// bilinear; for nearest the snapped tap nearbyint(pos) (round half to even, as ATen) expressed as
+// a fraction of exactly 0 or 1 -- the four bilinear weights then are one weight of 1 on that tap
+// and three exact zeros, and the fixed-point accumulation needs no other change.
+__device__ __forceinline__ float tap_fraction(float pos, float pos0, int interp) {
+    return interp == CERB_INTERP_NEAREST ? nearbyintf(pos) - pos0 : pos - pos0;
 }
 
 // Branch-free tap fetch: a tap outside the image reads a block of zeros instead of being

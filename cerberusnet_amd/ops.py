@@ -679,14 +679,9 @@ def _warp_ctx_setup(ctx, inputs, output):
 def _warp_ctx_backward(ctx, grad, _grad_context):
     image, flow, context = ctx.saved_tensors
     need_image, need_flow = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    if ctx.modes[1] != INTERP_MODES["bilinear"] or ctx.modes[0] == PAD_MODES["reflection"]:
-        context = None   # unsupported combinations raise in the raw op, as before
-        gi, gf = torch.ops.cerberus.flow_warp_backward(image, flow, grad, ctx.modes[0],
-                                                       ctx.modes[1], need_image, need_flow)
-    else:
-        gi, gf = torch.ops.cerberus.flow_warp_backward_ctx(image, flow, context, grad,
-                                                           ctx.modes[0], ctx.modes[1],
-                                                           need_image, need_flow)
+    gi, gf = torch.ops.cerberus.flow_warp_backward_ctx(image, flow, context, grad,
+                                                       ctx.modes[0], ctx.modes[1],
+                                                       need_image, need_flow)
     return (gi if need_image else None, gf.to(flow.dtype) if need_flow else None, None, None)
 
 

@@ -56,7 +56,7 @@ enum cerb_interp_mode { CERB_INTERP_BILINEAR = 0, CERB_INTERP_NEAREST = 1 };
 #define CERB_ESTRIDE1     -3  /* correlation backward with stride1 != 1 (reference is   */
                               /* memory-unsafe there, correlation_cuda_kernel.cu:106)   */
 #define CERB_EMODE        -4  /* unknown padding / interpolation mode                   */
-#define CERB_EUNSUPPORTED -5  /* valid but not implemented (reflection-pad backward)    */
+#define CERB_EUNSUPPORTED -5  /* valid but not implemented (reflection pad in the f2 fused warp) */
 #define CERB_ETOOLARGE    -6  /* a dimension exceeds 32-bit launch / index limits       */
 
 int cerberus_abi_version(void);
@@ -196,6 +196,10 @@ int cerberus_warp_correlation_forward(const void *input1, const void *input2, co
  *                cerberus_flow_warp_backward_workspace_bytes(B,C,H,W) bytes (16-byte
  *                aligned, contents irrelevant), private to this call until it completes;
  *                only needed when context is NULL.
+ * Every pad_mode x interp_mode pair is differentiable, with ATen's rules (align_corners = false):
+ * reflection multiplies the position gradient by the reflection's sign and zeroes it where the
+ * reflected position clips onto an edge; nearest adds grad_out to the nearbyint tap (ties to
+ * even) and writes grad_flow as exact zeros.
  * Either grad pointer may be NULL to skip that gradient. */
 int64_t cerberus_flow_warp_backward_workspace_bytes(int B, int C, int H, int W);
 int cerberus_flow_warp_backward(const void *image, const void *flow,
