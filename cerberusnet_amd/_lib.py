@@ -42,6 +42,12 @@ PROTOTYPES = {
     "cerberus_flow_upsample_backward": (_I, [_P, _P, _I64, _I, _I, _I, _I, _P]),
     "cerberus_area_resize": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _P]),
     "cerberus_area_pyramid": (_I, [_P, ctypes.POINTER(_P), ctypes.POINTER(_I), ctypes.POINTER(_I), _I, _I64, _I, _I, _I, _P]),
+    "cerberus_photometric_loss_workspace_bytes": (_I64, [_I] * 4),
+    "cerberus_photometric_loss_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 4 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_photometric_loss_backward": (_I, [_P, _P, _P, _P] + [_I] * 4 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
+    "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_set_option": (_I, [ctypes.c_char_p, _I]),
     "cerberus_get_option": (_I, [ctypes.c_char_p, ctypes.POINTER(_I)]),
     "cerberus_last_kernel": (ctypes.c_char_p, [_I]),

@@ -1,6 +1,6 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
-// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip and upsample.hip.
+// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip and photometric.hip.
 #include <atomic>
 #include <cstring>
 
@@ -297,6 +297,85 @@ int cerberus_area_pyramid(const void *src, void *const *dsts, const int *out_h, 
         if (r) return r;
     }
     return CERB_OK;
+}
+
+// the scalar loss ops are fp32 only: a known 16-bit / 64-bit dtype is "valid but not implemented"
+static int loss_dtype_ok(int dtype) {
+    if (!dtype_ok(dtype)) return CERB_EDTYPE;
+    return dtype == CERB_F32 ? CERB_OK : CERB_EUNSUPPORTED;
+}
+
+// one NCHW tensor's elements must be addressable with 32-bit offsets inside a batch item, the workgroups with an int
+static int loss_size_ok(int64_t B, int64_t C, int64_t H, int64_t W, int64_t workgroups) {
+    if (C * H * W > 0x7fffffff || workgroups > 0x7fffffff) return CERB_ETOOLARGE;
+    (void)B;
+    return CERB_OK;
+}
+
+static int photometric_args_ok(int B, int C, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B <= 0 || C <= 0 || H < 2 || W < 2) return CERB_EINVAL;     // ReflectionPad2d(1) needs two rows and columns
+    return loss_size_ok(B, C, H, W, photometric_workspace_bytes(B, C, H, W) / 4);
+}
+
+int64_t cerberus_photometric_loss_workspace_bytes(int B, int C, int H, int W) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
+    return photometric_workspace_bytes(B, C, H, W);
+}
+
+int cerberus_photometric_loss_forward(const void *im_orig, const void *im_recons, void *loss, void *workspace,
+                                      int64_t workspace_bytes, int B, int C, int H, int W, float l1_weight, float ssim_weight,
+                                      int dtype, void *stream) {
+    const int rc = photometric_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (!im_orig || !im_recons || !loss || !workspace) return CERB_EINVAL;
+    if (workspace_bytes < photometric_workspace_bytes(B, C, H, W)) return CERB_EINVAL;
+    return photometric_forward(im_orig, im_recons, loss, workspace, B, C, H, W, l1_weight, ssim_weight,
+                               static_cast<hipStream_t>(stream));
+}
+
+int cerberus_photometric_loss_backward(const void *im_orig, const void *im_recons, const void *grad_loss, void *grad_recons,
+                                       int B, int C, int H, int W, float l1_weight, float ssim_weight, int dtype, void *stream) {
+    const int rc = photometric_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (!im_orig || !im_recons || !grad_loss || !grad_recons) return CERB_EINVAL;
+    return photometric_backward(im_orig, im_recons, grad_loss, grad_recons, B, C, H, W, l1_weight, ssim_weight,
+                                static_cast<hipStream_t>(stream));
+}
+
+static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (degree != 1 && degree != 2) return CERB_EINVAL;
+    if (B <= 0 || Cf <= 0 || Ci <= 0 || H <= degree || W <= degree) return CERB_EINVAL;   // every term needs one element
+    return loss_size_ok(B, Cf > Ci ? Cf : Ci, H, W, smoothness_workspace_bytes(B, H, W) / 8);
+}
+
+int64_t cerberus_edge_smoothness_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return smoothness_workspace_bytes(B, H, W);
+}
+
+int cerberus_edge_smoothness_forward(const void *flow, const void *image, void *loss, void *workspace, int64_t workspace_bytes,
+                                     int B, int flow_channels, int image_channels, int H, int W, float alpha, int degree,
+                                     int dtype, void *stream) {
+    const int rc = smoothness_args_ok(B, flow_channels, image_channels, H, W, degree, dtype);
+    if (rc) return rc;
+    if (!flow || !image || !loss || !workspace) return CERB_EINVAL;
+    if (workspace_bytes < smoothness_workspace_bytes(B, H, W)) return CERB_EINVAL;
+    return smoothness_forward(flow, image, loss, workspace, B, flow_channels, image_channels, H, W, alpha, degree,
+                              static_cast<hipStream_t>(stream));
+}
+
+int cerberus_edge_smoothness_backward(const void *flow, const void *image, const void *grad_loss, void *grad_flow, int B,
+                                      int flow_channels, int image_channels, int H, int W, float alpha, int degree, int dtype,
+                                      void *stream) {
+    const int rc = smoothness_args_ok(B, flow_channels, image_channels, H, W, degree, dtype);
+    if (rc) return rc;
+    if (!flow || !image || !grad_loss || !grad_flow) return CERB_EINVAL;
+    return smoothness_backward(flow, image, grad_loss, grad_flow, B, flow_channels, image_channels, H, W, alpha, degree,
+                               static_cast<hipStream_t>(stream));
 }
 
 int cerberus_set_option(const char *key, int value) {

@@ -209,6 +209,19 @@ int area_resize(const void *src, void *dst, int64_t planes, int H, int W, int oH
 int area_pyramid(const void *src, void *const *dsts, const int *out_h, const int *out_w, int n, int64_t planes, int H,
                  int W, int dtype, hipStream_t s);
 
+// photometric.hip: unFlowLoss's photometric (L1 + SSIM) and edge-aware smoothness terms as scalar ops, fp32; arguments are
+// checked by api.hip.  `loss` / `grad_loss` point to ONE float in device memory.
+int64_t photometric_workspace_bytes(int B, int C, int H, int W);
+int photometric_forward(const void *orig, const void *recons, void *loss, void *workspace, int B, int C, int H, int W, float l1_w,
+                        float ssim_w, hipStream_t s);
+int photometric_backward(const void *orig, const void *recons, const void *grad_loss, void *grad_recons, int B, int C, int H, int W,
+                         float l1_w, float ssim_w, hipStream_t s);
+int64_t smoothness_workspace_bytes(int B, int H, int W);
+int smoothness_forward(const void *flow, const void *image, void *loss, void *workspace, int B, int Cf, int Ci, int H, int W,
+                       float alpha, int degree, hipStream_t s);
+int smoothness_backward(const void *flow, const void *image, const void *grad_loss, void *grad_flow, int B, int Cf, int Ci, int H,
+                        int W, float alpha, int degree, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

@@ -14,7 +14,8 @@ import torch
 
 from .. import ops as _ops
 
-__all__ = ["flow_warp", "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "unFlowLoss"]
+__all__ = ["flow_warp", "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness",
+           "unFlowLoss"]
 
 
 def area_resize(image, size):
@@ -104,6 +105,49 @@ def _edge_aware_smoothness(flow, image, alpha, degree):
     raise NotImplementedError(degree)
 
 
+def _photometric_stock(im_orig, im_recons, l1_weight, ssim_weight):
+    """The photometric term in stock ops (``loss_photometric`` below, all-ones mask); a weight of None or 0 skips its term."""
+    terms = []
+    if l1_weight:
+        terms.append(l1_weight * (im_orig - im_recons).abs())
+    if ssim_weight:
+        terms.append(ssim_weight * _ssim_distance(im_recons, im_orig))
+    if not terms:
+        return (im_recons * 0).sum()
+    return sum(t.mean() for t in terms)
+
+
+def _fusable(a, b):
+    """What the scalar HIP ops take: fp32 NCHW tensors on one GPU."""
+    return (a.is_cuda and b.is_cuda and a.device == b.device and a.dim() == 4 and b.dim() == 4
+            and a.dtype == torch.float32 and b.dtype == torch.float32 and a.numel() > 0)
+
+
+def photometric_loss(im_orig, im_recons, l1_weight=0.15, ssim_weight=0.85):
+    """mean(l1_weight * |im_orig - im_recons| + ssim_weight * clamp((1 - SSIM(im_recons, im_orig)) / 2, 0, 1)) as a 0-dim
+    tensor: ``unFlowLoss.loss_photometric`` (reference :236-255, all-ones mask) as ONE fused HIP forward and one fused
+    backward (``cerberus::photometric_loss``), differentiable in both images, reductions in a fixed order without
+    atomics.  A weight of None or 0 skips its term.  fp32 CUDA tensors with H, W >= 2 take the HIP op; anything else
+    (16-bit tensors, CPU tensors) the stock-op formulation."""
+    l1_weight, ssim_weight = float(l1_weight or 0.0), float(ssim_weight or 0.0)
+    if (_fusable(im_orig, im_recons) and im_orig.shape == im_recons.shape and min(im_orig.shape[2:]) >= 2
+            and (l1_weight or ssim_weight)):
+        return torch.ops.cerberus.photometric_loss(im_orig, im_recons, l1_weight, ssim_weight)
+    return _photometric_stock(im_orig, im_recons, l1_weight, ssim_weight)
+
+
+def edge_smoothness(flow, image, alpha, degree):
+    """``_edge_aware_smoothness`` (reference :162-187; degree 1 or 2) as one fused HIP forward and one gather backward
+    (``cerberus::edge_smoothness``), differentiable in the flow.  An image that requires grad, 16-bit or CPU tensors and
+    maps smaller than the degree needs take the stock-op formulation."""
+    if degree not in (1, 2):
+        raise NotImplementedError(degree)
+    if (_fusable(flow, image) and flow.shape[0] == image.shape[0] and flow.shape[2:] == image.shape[2:]
+            and min(flow.shape[2:]) > degree and not (torch.is_grad_enabled() and image.requires_grad)):
+        return torch.ops.cerberus.edge_smoothness(flow, image, float(alpha), int(degree))
+    return _edge_aware_smoothness(flow, image, alpha, degree)
+
+
 class unFlowLoss(torch.nn.Module):
     """Counterpart of ``unFlowLoss`` (:189-322) for the terms the Cerberus configs use: L1 and SSIM
     photometric terms on the image pair warped by the predicted flow at every pyramid scale,
@@ -113,10 +157,15 @@ class unFlowLoss(torch.nn.Module):
     (dead code in the reference, :285-297: the mask is all ones) are not built.
 
     ``backend='hip'`` (default): the two warps per scale are ``cerberus::flow_warp`` and the area
-    resizes of the targets ``cerberus::area_resize``; ``'torch'``: stock ops, CPU tests only."""
+    resizes of the targets ``cerberus::area_resize``; ``'torch'``: stock ops, CPU tests only.
+
+    ``fused=True`` (opt-in, ``backend='hip'`` only): what follows each warp -- the photometric term and the edge-aware
+    smoothness -- runs as ``photometric_loss`` / ``edge_smoothness`` above (one HIP launch pair each instead of ~35 / ~15
+    stock launches, reductions in a fixed order), per call where the op applies.  The default ``False`` keeps every
+    result as it was."""
 
     def __init__(self, weight=1.0, weights=None, consistency=True, back_occ_only=False,
-                 backend="hip", **kwargs):
+                 backend="hip", fused=False, **kwargs):
         super().__init__()
         weights = weights or {"l1": 0.15, "ssim": 0.85}
         if "ternary" in weights:
@@ -131,7 +180,14 @@ class unFlowLoss(torch.nn.Module):
         self.back_occ_only = back_occ_only
         if backend not in ("hip", "torch"):
             raise ValueError("backend must be 'hip' or 'torch'")
+        if fused and backend != "hip":
+            raise ValueError("fused=True needs backend='hip' (the fused terms are HIP ops)")
         self.backend = backend
+        self.fused = bool(fused)
+
+    def _fused(self):
+        # `backend` may be reassigned on a live object: fused has no effect unless the backend is 'hip' at call time
+        return self.fused and self.backend == "hip"
 
     def _pyramid(self, image, sizes):
         if self.backend == "hip":
@@ -143,12 +199,18 @@ class unFlowLoss(torch.nn.Module):
             else _torch_flow_warp(image, flow, pad="border")
 
     def loss_photometric(self, im_orig, im_recons):
+        if self._fused():
+            return photometric_loss(im_orig, im_recons, self.l1_weight, self.ssim_weight)
         terms = []
         if self.l1_weight is not None:
             terms.append(self.l1_weight * (im_orig - im_recons).abs())
         if self.ssim_weight is not None:
             terms.append(self.ssim_weight * _ssim_distance(im_recons, im_orig))
         return sum(t.mean() for t in terms)          # (/ mean of the all-ones mask = 1)
+
+    def loss_smooth(self, flow, image):
+        fn = edge_smoothness if self._fused() else _edge_aware_smoothness
+        return fn(flow, image, self.smooth_args["alpha"], self.smooth_args["degree"])
 
     def forward(self, predictions, targets):
         total_warp, total_smooth, s = 0., 0., 1.
@@ -166,12 +228,10 @@ class unFlowLoss(torch.nn.Module):
             if i == 0:
                 s = min(size)
             warp = self.loss_photometric(im1, self._warp(im2, f12))
-            smooth = _edge_aware_smoothness(f12 / s, im1, self.smooth_args["alpha"],
-                                            self.smooth_args["degree"])
+            smooth = self.loss_smooth(f12 / s, im1)
             if self.consistency:
                 warp = (warp + self.loss_photometric(im2, self._warp(im1, f21))) / 2.
-                smooth = (smooth + _edge_aware_smoothness(f21 / s, im2, self.smooth_args["alpha"],
-                                                          self.smooth_args["degree"])) / 2.
+                smooth = (smooth + self.loss_smooth(f21 / s, im2)) / 2.
             total_warp = total_warp + warp * self.w_wrp_scales[i]
             total_smooth = total_smooth + smooth * self.w_sm_scales[i]
         return self.weight * (total_warp + self.smooth_args["weighting"] * total_smooth)

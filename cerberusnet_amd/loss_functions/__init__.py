@@ -1,3 +1,3 @@
-from .UnFlowLoss import flow_warp, mesh_grid, norm_grid, unFlowLoss
+from .UnFlowLoss import edge_smoothness, flow_warp, mesh_grid, norm_grid, photometric_loss, unFlowLoss
 
-__all__ = ["flow_warp", "mesh_grid", "norm_grid", "unFlowLoss"]
+__all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoothness", "unFlowLoss"]

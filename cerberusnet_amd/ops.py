@@ -58,6 +58,12 @@ _def.define("flow_warp_backward_ctx(Tensor image, Tensor flow, Tensor context, T
 _def.define("flow_warp_backward(Tensor image, Tensor flow, Tensor grad_out, int pad_mode, "
             "int interp_mode, bool need_image, bool need_flow) -> Tensor[]")
 
+_def.define("photometric_loss(Tensor im_orig, Tensor im_recons, float l1_weight, float ssim_weight) -> Tensor")
+_def.define("photometric_loss_backward(Tensor im_orig, Tensor im_recons, Tensor grad_loss, float l1_weight, "
+            "float ssim_weight, bool need_orig, bool need_recons) -> Tensor[]")
+_def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
+_def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
+
 
 def _stream_ptr(t: torch.Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
@@ -539,6 +545,128 @@ def _area_pyramid_meta(image, sizes):
     return [image.new_empty((B, C, int(sizes[i]), int(sizes[i + 1]))) for i in range(0, len(sizes), 2)]
 
 
+# ----------------------------------------------------------------------------
+# unFlowLoss's scalar terms (UnFlowLoss.py:162-187, :236-255; loss_functions.py:47-77), csrc/photometric.hip
+# ----------------------------------------------------------------------------
+def _photometric_workspace_bytes(B, C, H, W):
+    """cerberus_photometric_loss_workspace_bytes in pure Python (a test holds the two equal): one fp32 partial per
+    16 x 64 tile of every image plane."""
+    if B <= 0 or C <= 0 or H <= 0 or W <= 0:
+        return 0
+    return ((W + 63) // 64) * ((H + 15) // 16) * B * C * 4
+
+
+def _smoothness_workspace_bytes(B, H, W):
+    """cerberus_edge_smoothness_workspace_bytes in pure Python: an x and a y partial per 4 x 64 tile of every batch item."""
+    if B <= 0 or H <= 0 or W <= 0:
+        return 0
+    return ((W + 63) // 64) * ((H + 3) // 4) * B * 8
+
+
+def _loss_check(a, b, what, names):
+    for t, name in zip((a, b), names):
+        if t.dim() != 4:
+            raise RuntimeError("%s: %s must be a 4-D NCHW tensor, got %s" % (what, name, tuple(t.shape)))
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s must be float32, got %s (16-bit tensors take the stock-op path of "
+                               "loss_functions.photometric_loss / edge_smoothness)" % (what, name, t.dtype))
+    if a.device != b.device:
+        raise RuntimeError("%s: inputs on different devices: %s vs %s" % (what, a.device, b.device))
+
+
+def _grad_scalar(grad_loss, like, what):
+    if grad_loss.numel() != 1:
+        raise RuntimeError("%s: grad_loss must hold one element, got %s" % (what, tuple(grad_loss.shape)))
+    # stays on the device: the kernel reads it (no .item(), no synchronisation -- capturable)
+    return grad_loss.to(device=like.device, dtype=torch.float32).contiguous()
+
+
+def _photometric_loss_cuda(im_orig, im_recons, l1_weight, ssim_weight):
+    what = "cerberus::photometric_loss"
+    _loss_check(im_orig, im_recons, what, ("im_orig", "im_recons"))
+    if im_orig.shape != im_recons.shape:
+        raise RuntimeError("%s: image shapes differ: %s vs %s" % (what, tuple(im_orig.shape), tuple(im_recons.shape)))
+    a, b = im_orig.contiguous(), im_recons.contiguous()
+    B, C, H, W = a.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_photometric_loss_workspace_bytes(B, C, H, W)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=a.device)
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.cerberus_photometric_loss_forward(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes, B, C, H, W,
+                                                   float(l1_weight), float(ssim_weight), 0, _stream_ptr(a))
+    _lib.check(rc, what)
+    return out
+
+
+def _photometric_loss_backward_cuda(im_orig, im_recons, grad_loss, l1_weight, ssim_weight, need_orig,
+                                    need_recons) -> List[torch.Tensor]:
+    what = "cerberus::photometric_loss_backward"
+    _loss_check(im_orig, im_recons, what, ("im_orig", "im_recons"))
+    if im_orig.shape != im_recons.shape:
+        raise RuntimeError("%s: image shapes differ: %s vs %s" % (what, tuple(im_orig.shape), tuple(im_recons.shape)))
+    a, b = im_orig.contiguous(), im_recons.contiguous()
+    g = _grad_scalar(grad_loss, a, what)
+    B, C, H, W = a.shape
+    lib = _lib.get()
+    outs = []
+    # the loss is symmetric in the two images: the gradient of im_orig is the same launch with the roles exchanged
+    for need, first, second in ((need_orig, b, a), (need_recons, a, b)):
+        if not need:
+            outs.append(a.new_empty((0,)))
+            continue
+        grad = torch.empty_like(second)
+        with torch.cuda.device(a.device):
+            rc = lib.cerberus_photometric_loss_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H, W,
+                                                        float(l1_weight), float(ssim_weight), 0, _stream_ptr(a))
+        _lib.check(rc, what)
+        outs.append(grad)
+    return outs
+
+
+def _photometric_loss_backward_meta(im_orig, im_recons, grad_loss, l1_weight, ssim_weight, need_orig, need_recons):
+    return [torch.empty_like(im_orig) if need_orig else im_orig.new_empty((0,)),
+            torch.empty_like(im_recons) if need_recons else im_recons.new_empty((0,))]
+
+
+def _smoothness_check(flow, image, degree, what):
+    _loss_check(flow, image, what, ("flow", "image"))
+    if flow.shape[0] != image.shape[0] or flow.shape[2:] != image.shape[2:]:
+        raise RuntimeError("%s: flow %s and image %s differ in batch or size" % (what, tuple(flow.shape), tuple(image.shape)))
+    if degree not in (1, 2):
+        raise RuntimeError("%s: degree must be 1 or 2, got %s" % (what, degree))
+
+
+def _edge_smoothness_cuda(flow, image, alpha, degree):
+    what = "cerberus::edge_smoothness"
+    _smoothness_check(flow, image, degree, what)
+    f, img = flow.contiguous(), image.contiguous()
+    B, Cf, H, W = f.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_edge_smoothness_workspace_bytes(B, H, W)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=f.device)
+    out = torch.empty((), dtype=torch.float32, device=f.device)
+    with torch.cuda.device(f.device):
+        rc = lib.cerberus_edge_smoothness_forward(f.data_ptr(), img.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes, B, Cf,
+                                                  img.shape[1], H, W, float(alpha), int(degree), 0, _stream_ptr(f))
+    _lib.check(rc, what)
+    return out
+
+
+def _edge_smoothness_backward_cuda(flow, image, grad_loss, alpha, degree):
+    what = "cerberus::edge_smoothness_backward"
+    _smoothness_check(flow, image, degree, what)
+    f, img = flow.contiguous(), image.contiguous()
+    g = _grad_scalar(grad_loss, f, what)
+    B, Cf, H, W = f.shape
+    grad = torch.empty_like(f)
+    with torch.cuda.device(f.device):
+        rc = _lib.get().cerberus_edge_smoothness_backward(f.data_ptr(), img.data_ptr(), g.data_ptr(), grad.data_ptr(), B, Cf,
+                                                          img.shape[1], H, W, float(alpha), int(degree), 0, _stream_ptr(f))
+    _lib.check(rc, what)
+    return grad
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -558,6 +686,18 @@ _def.impl("warp_correlation_leaky", _no_cpu("warp_correlation_leaky"), "CPU")
 _def.impl("correlation_leaky_into", _correlation_leaky_into_cuda, "CUDA")
 _def.impl("correlation_leaky_into", lambda *a: None, "Meta")
 _def.impl("correlation_leaky_into", _no_cpu("correlation_leaky_into"), "CPU")
+_def.impl("photometric_loss", _photometric_loss_cuda, "CUDA")
+_def.impl("photometric_loss", lambda a, b, l1, ss: a.new_empty((), dtype=torch.float32), "Meta")
+_def.impl("photometric_loss", _no_cpu("photometric_loss"), "CPU")
+_def.impl("photometric_loss_backward", _photometric_loss_backward_cuda, "CUDA")
+_def.impl("photometric_loss_backward", _photometric_loss_backward_meta, "Meta")
+_def.impl("photometric_loss_backward", _no_cpu("photometric_loss_backward"), "CPU")
+_def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
+_def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
+_def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
+_def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
+_def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
+_def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
 _def.impl("correlation_backward", _correlation_backward_cuda, "CUDA")
 _def.impl("correlation_backward", _correlation_backward_meta, "Meta")
 _def.impl("correlation_backward", _no_cpu("correlation_backward"), "CPU")
@@ -719,3 +859,46 @@ torch.library.register_autograd("cerberus::flow_warp", _warp_backward,
                                 setup_context=_warp_setup)
 torch.library.register_autograd("cerberus::flow_warp_ctx", _warp_ctx_backward,
                                 setup_context=_warp_ctx_setup)
+
+
+def _photometric_setup(ctx, inputs, output):
+    im_orig, im_recons, l1_weight, ssim_weight = inputs
+    ctx.save_for_backward(im_orig, im_recons)       # nothing but the inputs: the backward recomputes
+    ctx.weights = (l1_weight, ssim_weight)
+
+
+def _photometric_backward(ctx, grad):
+    im_orig, im_recons = ctx.saved_tensors
+    need_orig, need_recons = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    go, gr = torch.ops.cerberus.photometric_loss_backward(im_orig, im_recons, grad, ctx.weights[0], ctx.weights[1],
+                                                          need_orig, need_recons)
+    return (go if need_orig else None, gr if need_recons else None, None, None)
+
+
+def _smoothness_setup(ctx, inputs, output):
+    flow, image, alpha, degree = inputs
+    ctx.save_for_backward(flow, image)
+    ctx.params = (alpha, degree)
+
+
+def _smoothness_backward(ctx, grad):
+    flow, image = ctx.saved_tensors
+    if ctx.needs_input_grad[1]:
+        raise RuntimeError("cerberus::edge_smoothness has no gradient for its image (a target image in unFlowLoss): "
+                           "loss_functions.edge_smoothness takes the stock-op path for an image that requires grad")
+    gf = torch.ops.cerberus.edge_smoothness_backward(flow, image, grad, *ctx.params) if ctx.needs_input_grad[0] else None
+    return gf, None, None, None
+
+
+def _no_double_backward(name):
+    def _raise(ctx, *grads):
+        raise RuntimeError("cerberus::%s is not differentiable (no double backward)" % name)
+    return _raise
+
+
+torch.library.register_autograd("cerberus::photometric_loss", _photometric_backward, setup_context=_photometric_setup)
+torch.library.register_autograd("cerberus::edge_smoothness", _smoothness_backward, setup_context=_smoothness_setup)
+torch.library.register_autograd("cerberus::photometric_loss_backward", _no_double_backward("photometric_loss_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::edge_smoothness_backward", _no_double_backward("edge_smoothness_backward"),
+                                setup_context=lambda ctx, inputs, output: None)

@@ -242,6 +242,55 @@ int cerberus_area_resize(const void *src, void *dst, int64_t planes, int H, int 
 int cerberus_area_pyramid(const void *src, void *const *dsts, const int *out_h, const int *out_w,
                           int n_scales, int64_t planes, int H, int W, int dtype, void *stream);
 
+/* unFlowLoss's photometric term as ONE differentiable scalar (no ABI bump: additions only).  Replaces, per call,
+ * loss_photometric with its all-ones mask (nnet_training/loss_functions/UnFlowLoss.py:236-255) over SSIM
+ * (loss_functions.py:47-77): 2 reflection pads, 5 average pools, ~20 elementwise launches and two whole-tensor means.
+ *   loss[0] = mean over all B*C*H*W elements of
+ *             l1_weight * |im_orig - im_recons| + ssim_weight * clamp((1 - SSIM(im_recons, im_orig)) / 2, 0, 1)
+ * SSIM per channel on 3 x 3 windows behind a reflection padding of 1 (row -1 is row 1), C1 = 0.01^2, C2 = 0.03^2.
+ * A weight of 0 skips its term (it is not multiplied: a NaN pixel then does not reach the result through it).
+ *   im_orig, im_recons : (B,C,H,W) fp32, H, W >= 2        loss : ONE float in device memory, overwritten
+ *   workspace          : cerberus_photometric_loss_workspace_bytes(B,C,H,W) bytes (one partial sum per 16 x 64 tile;
+ *                        0 for a non-positive size), fully overwritten; no zero-fill needed
+ * Forward: a tile kernel (both images + 1-pixel halo in LDS, one partial per workgroup) and a single-workgroup launch
+ * that adds the partials in a fixed order: no floating-point atomics, bit-reproducible for a given shape.
+ * Backward: grad_recons (B,C,H,W) = grad_loss[0] * d loss / d im_recons, every element written exactly once (no
+ * zero-fill, no atomics), recomputed from the two images alone.  grad_loss points to ONE float in DEVICE memory (no
+ * host synchronisation: the call can be captured in a graph).  clamp passes the gradient where its argument lies in
+ * [0, 1] (bounds included), |.| has gradient 0 at equality (ATen's rules).  The loss is symmetric in the two images:
+ * the gradient with respect to im_orig is the same call with the two image pointers exchanged.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; empty tensors, H or W < 2, a null pointer,
+ * a workspace that is too small CERB_EINVAL; C*H*W >= 2^31 CERB_ETOOLARGE -- all before any launch. */
+int64_t cerberus_photometric_loss_workspace_bytes(int B, int C, int H, int W);
+int cerberus_photometric_loss_forward(const void *im_orig, const void *im_recons, void *loss,
+                                      void *workspace, int64_t workspace_bytes, int B, int C, int H,
+                                      int W, float l1_weight, float ssim_weight, int dtype,
+                                      void *stream);
+int cerberus_photometric_loss_backward(const void *im_orig, const void *im_recons,
+                                       const void *grad_loss, void *grad_recons, int B, int C, int H,
+                                       int W, float l1_weight, float ssim_weight, int dtype,
+                                       void *stream);
+
+/* unFlowLoss's edge-aware smoothness term as one differentiable scalar.  Replaces _edge_aware_smoothness
+ * (UnFlowLoss.py:162-187), ~15 launches per call:
+ *   wx = exp(-alpha * mean_c |image[..., 1:] - image[..., :-1]|), wy likewise along rows
+ *   degree 1: loss = (mean(wx * |dx flow| / 2) + mean(wy * |dy flow| / 2)) / 2
+ *   degree 2: loss = (mean(wx[..., 1:] * |dx dx flow|) + mean(wy[..., 1:, :] * |dy dy flow|)) / 2
+ * (the x and the y term are means over DIFFERENT element counts, then averaged).
+ *   flow (B,flow_channels,H,W), image (B,image_channels,H,W), fp32; H, W > degree
+ *   workspace : cerberus_edge_smoothness_workspace_bytes(B,H,W) bytes (an x and a y partial per 4 x 64 tile)
+ * Same reduction scheme as above.  Backward: grad_flow = grad_loss[0] * d loss / d flow, a pure gather per flow element
+ * (it appears in at most degree + 1 differences per axis), every element written once; there is no gradient for the
+ * image (a target image).  Errors as above; a degree other than 1 or 2 is CERB_EINVAL. */
+int64_t cerberus_edge_smoothness_workspace_bytes(int B, int H, int W);
+int cerberus_edge_smoothness_forward(const void *flow, const void *image, void *loss, void *workspace,
+                                     int64_t workspace_bytes, int B, int flow_channels,
+                                     int image_channels, int H, int W, float alpha, int degree,
+                                     int dtype, void *stream);
+int cerberus_edge_smoothness_backward(const void *flow, const void *image, const void *grad_loss,
+                                      void *grad_flow, int B, int flow_channels, int image_channels,
+                                      int H, int W, float alpha, int degree, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
