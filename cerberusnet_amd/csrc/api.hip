@@ -1,6 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
-// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip and photometric.hip.
+// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip and
+// census.hip.
 #include <atomic>
 #include <cstring>
 
@@ -342,6 +343,37 @@ int cerberus_photometric_loss_backward(const void *im_orig, const void *im_recon
     if (!im_orig || !im_recons || !grad_loss || !grad_recons) return CERB_EINVAL;
     return photometric_backward(im_orig, im_recons, grad_loss, grad_recons, B, C, H, W, l1_weight, ssim_weight,
                                 static_cast<hipStream_t>(stream));
+}
+
+static int census_args_ok(int B, int H, int W, int max_distance, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (max_distance < 1 || max_distance > 3) return CERB_EINVAL;    // the compiled window sizes: 3 x 3, 5 x 5, 7 x 7
+    const int patch = 2 * max_distance + 1;
+    if (B <= 0 || H < patch || W < patch) return CERB_EINVAL;        // the valid mask needs one interior pixel
+    return loss_size_ok(B, 3, H, W, census_workspace_bytes(B, H, W) / 4);
+}
+
+int64_t cerberus_census_loss_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return census_workspace_bytes(B, H, W);
+}
+
+int cerberus_census_loss_forward(const void *im, const void *im_warp, void *loss, void *workspace, int64_t workspace_bytes, int B,
+                                 int H, int W, int max_distance, int dtype, void *stream) {
+    const int rc = census_args_ok(B, H, W, max_distance, dtype);
+    if (rc) return rc;
+    if (!im || !im_warp || !loss || !workspace) return CERB_EINVAL;
+    if (workspace_bytes < census_workspace_bytes(B, H, W)) return CERB_EINVAL;
+    return census_forward(im, im_warp, loss, workspace, B, H, W, max_distance, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_census_loss_backward(const void *im, const void *im_warp, const void *grad_loss, void *grad_warp, int B, int H, int W,
+                                  int max_distance, int dtype, void *stream) {
+    const int rc = census_args_ok(B, H, W, max_distance, dtype);
+    if (rc) return rc;
+    if (!im || !im_warp || !grad_loss || !grad_warp) return CERB_EINVAL;
+    return census_backward(im, im_warp, grad_loss, grad_warp, B, H, W, max_distance, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

@@ -222,6 +222,14 @@ int smoothness_forward(const void *flow, const void *image, void *loss, void *wo
 int smoothness_backward(const void *flow, const void *image, const void *grad_loss, void *grad_flow, int B, int Cf, int Ci, int H,
                         int W, float alpha, int degree, hipStream_t s);
 
+// census.hip: unFlowLoss's census (ternary) term as a scalar op, fp32, 3 channels, max_distance 1..3; arguments are checked by
+// api.hip.  `loss` / `grad_loss` point to ONE float in device memory.
+int64_t census_workspace_bytes(int B, int H, int W);
+int census_forward(const void *im, const void *im_warp, void *loss, void *workspace, int B, int H, int W, int max_distance,
+                   hipStream_t s);
+int census_backward(const void *im, const void *im_warp, const void *grad_loss, void *grad_warp, int B, int H, int W,
+                    int max_distance, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

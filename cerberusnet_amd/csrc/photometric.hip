@@ -19,6 +19,7 @@
 // p whose reflected window holds q (m = how often), with A' = dV/dmu_x at fixed variance / covariance, B = dV/dvar_x,
 // C = dV/dcov -- algebraically (sum A + 2 x_q sum B + y_q sum C) / 9 with A = A' - 2 mu_x B - mu_y C.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace cerb {
 namespace {
@@ -26,7 +27,7 @@ namespace {
 constexpr int kTW = 64;        // tile: one column per lane ...
 constexpr int kTH = 16;        // ... and 4 consecutive rows per thread, 4 waves
 constexpr int kRows = 4;
-constexpr int kThreads = 256;
+constexpr int kThreads = kReduceThreads;
 constexpr float kC1 = 1e-4f;   // 0.01 ** 2
 constexpr float kC2 = 9e-4f;   // 0.03 ** 2
 constexpr float kNinth = 1.0f / 9.0f;
@@ -38,21 +39,6 @@ __device__ __forceinline__ int reflect1(int p, int n) {
     p = p < 0 ? -p : p;
     p = p >= n ? 2 * n - 2 - p : p;
     return min(max(p, 0), n - 1);
-}
-
-// the same fold in every lane and every run: the order of a butterfly does not depend on timing
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup's 4 waves in wave order (every thread returns the same value)
-__device__ __forceinline__ float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // torch.clamp(v, 0, 1): a NaN stays a NaN (fminf / fmaxf would drop it)
@@ -151,29 +137,6 @@ __global__ __launch_bounds__(kThreads) void photometric_fwd_kernel(const float *
     }
     const float total = block_sum(acc, red);
     if (threadIdx.x == 0) partials[blk] = total;
-}
-
-// ---- the second launch of every reduction: one workgroup, fixed order ---------------------------------------------
-// out[0] = (sum(p0[0..n)) / count0 + sum(p1[0..n)) / count1) * scale; p1 may be null
-__global__ __launch_bounds__(kThreads) void final_sum_kernel(const float *__restrict__ p0, const float *__restrict__ p1, int n,
-                                                             float count0, float count1, float scale, float *__restrict__ out) {
-    __shared__ float red[2][kThreads];
-    float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < n; i += kThreads) {
-        a += p0[i];
-        if (p1) b += p1[i];
-    }
-    red[0][threadIdx.x] = a;
-    red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = p1 ? (red[0][0] / count0 + red[1][0] / count1) * scale : (red[0][0] / count0) * scale;
 }
 
 // ---- photometric backward -----------------------------------------------------------------------------------------

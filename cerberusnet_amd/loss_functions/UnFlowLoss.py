@@ -15,7 +15,7 @@ import torch
 from .. import ops as _ops
 
 __all__ = ["flow_warp", "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness",
-           "unFlowLoss"]
+           "TernaryLoss", "census_loss", "unFlowLoss"]
 
 
 def area_resize(image, size):
@@ -91,6 +91,30 @@ def _ssim_distance(x, y):
     return torch.clamp((1 - num / den) / 2, 0, 1)
 
 
+def TernaryLoss(im, im_warp, max_distance=1):
+    """The census ("ternary") distance map of two RGB images, (B,1,H,W), zero within ``max_distance`` of the border
+    (reference :119-156, same name, signature and return value) in stock ops: the soft ternary transform
+    ``t = x / sqrt(0.81 + x^2)`` of every gray difference ``x`` inside a ``2 * max_distance + 1`` window, and the mean over
+    the window of ``D / (0.1 + D)``, ``D = (t(im) - t(im_warp))^2``.  The formulation ``census_loss`` falls back to, the
+    CPU path and the tests' yardstick."""
+    import torch.nn.functional as F
+    patch_size = 2 * max_distance + 1
+    out_channels = patch_size * patch_size
+    weights = torch.eye(out_channels).view((out_channels, 1, patch_size, patch_size)).type_as(im)
+
+    def transform(image):
+        gray = image[:, 0, :, :] * 0.2989 + image[:, 1, :, :] * 0.5870 + image[:, 2, :, :] * 0.1140
+        intensities = gray.unsqueeze(1) * 255
+        transf = F.conv2d(intensities, weights, padding=max_distance) - intensities
+        return transf / torch.sqrt(0.81 + torch.pow(transf, 2))
+
+    dist = torch.pow(transform(im) - transform(im_warp), 2)
+    dist_mean = torch.mean(dist / (0.1 + dist), 1, keepdim=True)
+    n, _, h, w = im.size()
+    inner = torch.ones(n, 1, h - 2 * max_distance, w - 2 * max_distance).type_as(im)
+    return dist_mean * F.pad(inner, [max_distance] * 4)
+
+
 def _edge_aware_smoothness(flow, image, alpha, degree):
     """First / second order smoothness of the flow, damped across image edges (:162-187)."""
     dx = lambda t: t[:, :, :, 1:] - t[:, :, :, :-1]
@@ -148,13 +172,29 @@ def edge_smoothness(flow, image, alpha, degree):
     return _edge_aware_smoothness(flow, image, alpha, degree)
 
 
+def census_loss(im, im_warp, max_distance=1):
+    """``TernaryLoss(im, im_warp, max_distance).mean()`` as a 0-dim tensor: the census term of ``loss_photometric``
+    (reference :237-239, all-ones mask) as ONE fused HIP forward and one fused backward (``cerberus::census_loss``),
+    differentiable in both images, reduced in a fixed order without atomics.  fp32 CUDA tensors of equal shape with 3
+    channels, ``max_distance`` 1, 2 or 3 and H, W >= 2 * max_distance + 1 take the HIP op; anything else (16-bit or CPU
+    tensors, other windows) the stock-op formulation."""
+    if (_fusable(im, im_warp) and im.shape == im_warp.shape and im.shape[1] == 3
+            and max_distance in _ops.CENSUS_MAX_DISTANCES and min(im.shape[2:]) >= 2 * max_distance + 1):
+        return torch.ops.cerberus.census_loss(im, im_warp, int(max_distance))
+    return TernaryLoss(im, im_warp, max_distance).mean()
+
+
 class unFlowLoss(torch.nn.Module):
     """Counterpart of ``unFlowLoss`` (:189-322) for the terms the Cerberus configs use: L1 and SSIM
     photometric terms on the image pair warped by the predicted flow at every pyramid scale,
     edge-aware smoothness, forward / backward consistency.  Same constructor keywords, same
     ``forward(predictions, targets)`` with ``predictions['flow'|'flow_b']`` (lists, full resolution
-    first) and ``targets['l_img'|'l_seq']``.  The census ("ternary") term and the occlusion masks
-    (dead code in the reference, :285-297: the mask is all ones) are not built.
+    first) and ``targets['l_img'|'l_seq']``.  The occlusion masks (dead code in the reference, :285-297: the mask is
+    all ones) are not built.
+
+    ``weights`` may carry ``"ternary"``, the census term (``TernaryLoss`` above, added to the photometric term as in the
+    reference, :237-239), with ``fused=True`` (``census_loss``, the HIP op) or ``backend='torch'`` (stock ops).  With the
+    defaults (``backend='hip'``, ``fused=False``) a ternary weight raises ``NotImplementedError``.
 
     ``backend='hip'`` (default): the two warps per scale are ``cerberus::flow_warp`` and the area
     resizes of the targets ``cerberus::area_resize``; ``'torch'``: stock ops, CPU tests only.
@@ -168,18 +208,20 @@ class unFlowLoss(torch.nn.Module):
                  backend="hip", fused=False, **kwargs):
         super().__init__()
         weights = weights or {"l1": 0.15, "ssim": 0.85}
-        if "ternary" in weights:
-            raise NotImplementedError("the census (ternary) term is outside the hot-path scope")
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if "ternary" in weights and not (fused or backend == "torch"):
+            raise NotImplementedError("the census (ternary) term runs as the fused HIP op census_loss: pass fused=True "
+                                      "(or backend='torch' for the stock-op formulation)")
         self.weight = weight
         self.l1_weight = weights.get("l1")
         self.ssim_weight = weights.get("ssim")
+        self.ternary_weight = weights.get("ternary")
         self.smooth_args = kwargs.get("smooth", {"degree": 2, "alpha": 0.2, "weighting": 75.0})
         self.w_sm_scales = kwargs.get("w_sm_scales", [1.0, 0.0, 0.0, 0.0, 0.0])
         self.w_wrp_scales = kwargs.get("w_wrp_scales", [1.0, 1.0, 1.0, 1.0, 0.0])
         self.consistency = consistency
         self.back_occ_only = back_occ_only
-        if backend not in ("hip", "torch"):
-            raise ValueError("backend must be 'hip' or 'torch'")
         if fused and backend != "hip":
             raise ValueError("fused=True needs backend='hip' (the fused terms are HIP ops)")
         self.backend = backend
@@ -200,12 +242,21 @@ class unFlowLoss(torch.nn.Module):
 
     def loss_photometric(self, im_orig, im_recons):
         if self._fused():
-            return photometric_loss(im_orig, im_recons, self.l1_weight, self.ssim_weight)
+            loss = photometric_loss(im_orig, im_recons, self.l1_weight, self.ssim_weight)
+            if self.ternary_weight is not None:
+                if not (self.l1_weight or self.ssim_weight):
+                    return self.ternary_weight * census_loss(im_recons, im_orig)
+                loss = loss + self.ternary_weight * census_loss(im_recons, im_orig)
+            return loss
         terms = []
         if self.l1_weight is not None:
             terms.append(self.l1_weight * (im_orig - im_recons).abs())
         if self.ssim_weight is not None:
             terms.append(self.ssim_weight * _ssim_distance(im_recons, im_orig))
+        if self.ternary_weight is not None:
+            if self.backend != "torch":        # `backend` may be reassigned on a live object
+                raise NotImplementedError("the census (ternary) term needs fused=True or backend='torch'")
+            terms.append(self.ternary_weight * TernaryLoss(im_recons, im_orig))
         return sum(t.mean() for t in terms)          # (/ mean of the all-ones mask = 1)
 
     def loss_smooth(self, flow, image):

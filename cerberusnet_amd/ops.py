@@ -61,6 +61,9 @@ _def.define("flow_warp_backward(Tensor image, Tensor flow, Tensor grad_out, int 
 _def.define("photometric_loss(Tensor im_orig, Tensor im_recons, float l1_weight, float ssim_weight) -> Tensor")
 _def.define("photometric_loss_backward(Tensor im_orig, Tensor im_recons, Tensor grad_loss, float l1_weight, "
             "float ssim_weight, bool need_orig, bool need_recons) -> Tensor[]")
+_def.define("census_loss(Tensor im, Tensor im_warp, int max_distance) -> Tensor")
+_def.define("census_loss_backward(Tensor im, Tensor im_warp, Tensor grad_loss, int max_distance, bool need_im, "
+            "bool need_warp) -> (Tensor, Tensor)")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -667,6 +670,83 @@ def _edge_smoothness_backward_cuda(flow, image, grad_loss, alpha, degree):
     return grad
 
 
+# the census (ternary) term (UnFlowLoss.py:119-156), csrc/census.hip
+CENSUS_MAX_DISTANCES = (1, 2, 3)        # the compiled window sizes: 3 x 3, 5 x 5, 7 x 7
+
+
+def _census_workspace_bytes(B, H, W):
+    """cerberus_census_loss_workspace_bytes in pure Python (a test holds the two equal): one fp32 partial per 16 x 64
+    tile of every batch item."""
+    if B <= 0 or H <= 0 or W <= 0:
+        return 0
+    return ((W + 63) // 64) * ((H + 15) // 16) * B * 4
+
+
+def _census_check(im, im_warp, max_distance, what):
+    for t, name in zip((im, im_warp), ("im", "im_warp")):
+        if t.dim() != 4:
+            raise RuntimeError("%s: %s must be a 4-D NCHW tensor, got %s" % (what, name, tuple(t.shape)))
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s must be float32, got %s (16-bit tensors take the stock-op path of "
+                               "loss_functions.census_loss)" % (what, name, t.dtype))
+    if im.device != im_warp.device:
+        raise RuntimeError("%s: inputs on different devices: %s vs %s" % (what, im.device, im_warp.device))
+    if im.shape != im_warp.shape:
+        raise RuntimeError("%s: image shapes differ: %s vs %s" % (what, tuple(im.shape), tuple(im_warp.shape)))
+    if im.shape[1] != 3:
+        raise RuntimeError("%s: the grayscale conversion needs 3 channels, got %d" % (what, im.shape[1]))
+    if max_distance not in CENSUS_MAX_DISTANCES:
+        raise RuntimeError("%s: max_distance must be one of %s, got %s (other windows take the stock-op path of "
+                           "loss_functions.census_loss)" % (what, CENSUS_MAX_DISTANCES, max_distance))
+    patch = 2 * max_distance + 1
+    if im.shape[0] < 1 or min(im.shape[2:]) < patch:
+        raise RuntimeError("%s: max_distance=%d needs a non-empty batch of maps of at least %d x %d, got %s"
+                           % (what, max_distance, patch, patch, tuple(im.shape)))
+
+
+def _census_loss_cuda(im, im_warp, max_distance):
+    what = "cerberus::census_loss"
+    _census_check(im, im_warp, max_distance, what)
+    a, b = im.contiguous(), im_warp.contiguous()
+    B, _, H, W = a.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_census_loss_workspace_bytes(B, H, W)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=a.device)
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = lib.cerberus_census_loss_forward(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes, B, H, W,
+                                              int(max_distance), 0, _stream_ptr(a))
+    _lib.check(rc, what)
+    return out
+
+
+def _census_loss_backward_cuda(im, im_warp, grad_loss, max_distance, need_im, need_warp):
+    what = "cerberus::census_loss_backward"
+    _census_check(im, im_warp, max_distance, what)
+    a, b = im.contiguous(), im_warp.contiguous()
+    g = _grad_scalar(grad_loss, a, what)
+    B, _, H, W = a.shape
+    lib = _lib.get()
+    outs = []
+    # the loss is symmetric in the two images: the gradient of im is the same launch with the roles exchanged
+    for need, first, second in ((need_im, b, a), (need_warp, a, b)):
+        if not need:
+            outs.append(a.new_empty((0,)))
+            continue
+        grad = torch.empty_like(second)
+        with torch.cuda.device(a.device):
+            rc = lib.cerberus_census_loss_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), grad.data_ptr(), B, H, W,
+                                                   int(max_distance), 0, _stream_ptr(a))
+        _lib.check(rc, what)
+        outs.append(grad)
+    return outs[0], outs[1]
+
+
+def _census_loss_backward_meta(im, im_warp, grad_loss, max_distance, need_im, need_warp):
+    return (torch.empty_like(im) if need_im else im.new_empty((0,)),
+            torch.empty_like(im_warp) if need_warp else im_warp.new_empty((0,)))
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -692,6 +772,12 @@ _def.impl("photometric_loss", _no_cpu("photometric_loss"), "CPU")
 _def.impl("photometric_loss_backward", _photometric_loss_backward_cuda, "CUDA")
 _def.impl("photometric_loss_backward", _photometric_loss_backward_meta, "Meta")
 _def.impl("photometric_loss_backward", _no_cpu("photometric_loss_backward"), "CPU")
+_def.impl("census_loss", _census_loss_cuda, "CUDA")
+_def.impl("census_loss", lambda a, b, d: a.new_empty((), dtype=torch.float32), "Meta")
+_def.impl("census_loss", _no_cpu("census_loss"), "CPU")
+_def.impl("census_loss_backward", _census_loss_backward_cuda, "CUDA")
+_def.impl("census_loss_backward", _census_loss_backward_meta, "Meta")
+_def.impl("census_loss_backward", _no_cpu("census_loss_backward"), "CPU")
 _def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
 _def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
 _def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
@@ -875,6 +961,19 @@ def _photometric_backward(ctx, grad):
     return (go if need_orig else None, gr if need_recons else None, None, None)
 
 
+def _census_setup(ctx, inputs, output):
+    im, im_warp, max_distance = inputs
+    ctx.save_for_backward(im, im_warp)              # nothing but the inputs: the backward recomputes
+    ctx.max_distance = max_distance
+
+
+def _census_backward(ctx, grad):
+    im, im_warp = ctx.saved_tensors
+    need_im, need_warp = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    gi, gw = torch.ops.cerberus.census_loss_backward(im, im_warp, grad, ctx.max_distance, need_im, need_warp)
+    return (gi if need_im else None, gw if need_warp else None, None)
+
+
 def _smoothness_setup(ctx, inputs, output):
     flow, image, alpha, degree = inputs
     ctx.save_for_backward(flow, image)
@@ -898,6 +997,9 @@ def _no_double_backward(name):
 
 torch.library.register_autograd("cerberus::photometric_loss", _photometric_backward, setup_context=_photometric_setup)
 torch.library.register_autograd("cerberus::edge_smoothness", _smoothness_backward, setup_context=_smoothness_setup)
+torch.library.register_autograd("cerberus::census_loss", _census_backward, setup_context=_census_setup)
+torch.library.register_autograd("cerberus::census_loss_backward", _no_double_backward("census_loss_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::photometric_loss_backward", _no_double_backward("photometric_loss_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::edge_smoothness_backward", _no_double_backward("edge_smoothness_backward"),

@@ -291,6 +291,36 @@ int cerberus_edge_smoothness_backward(const void *flow, const void *image, const
                                       void *grad_flow, int B, int flow_channels, int image_channels,
                                       int H, int W, float alpha, int degree, int dtype, void *stream);
 
+/* unFlowLoss's census ("ternary") term as one differentiable scalar (additions only: no ABI bump).  Replaces
+ * TernaryLoss(im, im_warp, max_distance).mean() (UnFlowLoss.py:119-156 and :237-239 with its all-ones mask): a grayscale
+ * conversion, an identity-kernel conv2d into K = (2 max_distance + 1)^2 planes, ~10 elementwise launches per image over
+ * those planes, a channel mean, a mask multiply and a whole-tensor mean.
+ *   gray = 255 (0.2989 R + 0.5870 G + 0.1140 B);  for every offset o of the window  x_o(q) = gray(q + o) - gray(q),
+ *   t_o = x_o / sqrt(0.81 + x_o^2);  D_o = (t_o(im) - t_o(im_warp))^2;  dist(q) = (1 / K) sum_o D_o / (0.1 + D_o)
+ *   loss[0] = sum of dist(q) over max_distance <= y < H - max_distance, max_distance <= x < W - max_distance, / (B*H*W)
+ * (the mean keeps the masked border in its denominator, as the reference's does).
+ *   im, im_warp : (B,3,H,W) fp32; max_distance 1, 2 or 3; H, W >= 2 max_distance + 1
+ *   loss        : ONE float in device memory, overwritten
+ *   workspace   : cerberus_census_loss_workspace_bytes(B,H,W) bytes (one partial sum per 16 x 64 tile of every batch
+ *                 item; 0 for a non-positive size), fully overwritten; no zero-fill needed
+ * Forward: a tile kernel (the GRAY planes of both images + a halo of max_distance in LDS, one partial per workgroup) and
+ * the single-workgroup fixed-order sum of the photometric op: no floating-point atomics, bit-reproducible for a given
+ * shape.  The mask selects: a NaN in any pixel reaches the result through an interior neighbour, a masked pixel adds 0.
+ * Backward: grad_warp (B,3,H,W) = grad_loss[0] * d loss / d im_warp, every element written exactly once (no zero-fill,
+ * no atomics), recomputed from the two images; grad_loss points to ONE float in DEVICE memory (no host synchronisation:
+ * capturable).  The loss is symmetric in the two images: the gradient with respect to im is the same call with the two
+ * image pointers exchanged.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; max_distance outside 1..3, B <= 0, H or W
+ * < 2 max_distance + 1, a null pointer, a workspace that is too small CERB_EINVAL; 3*H*W >= 2^31 CERB_ETOOLARGE -- all
+ * before any launch. */
+int64_t cerberus_census_loss_workspace_bytes(int B, int H, int W);
+int cerberus_census_loss_forward(const void *im, const void *im_warp, void *loss, void *workspace,
+                                 int64_t workspace_bytes, int B, int H, int W, int max_distance,
+                                 int dtype, void *stream);
+int cerberus_census_loss_backward(const void *im, const void *im_warp, const void *grad_loss,
+                                  void *grad_warp, int B, int H, int W, int max_distance, int dtype,
+                                  void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
