@@ -48,6 +48,9 @@ PROTOTYPES = {
     "cerberus_census_loss_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_census_loss_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [_P]),
     "cerberus_census_loss_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),
+    "cerberus_corresponding_map_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_corresponding_map": (_I, [_P, _P, _P, _I64] + [_I] * 5 + [_P]),
+    "cerberus_occlusion_mask_bidirection": (_I, [_P, _P, _P] + [_I] * 3 + [ctypes.c_float, ctypes.c_float, _I, _P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

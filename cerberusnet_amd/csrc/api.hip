@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
-// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip and
-// census.hip.
+// corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
+// census.hip and occlusion.hip.
 #include <atomic>
 #include <cstring>
 
@@ -374,6 +374,41 @@ int cerberus_census_loss_backward(const void *im, const void *im_warp, const voi
     if (rc) return rc;
     if (!im || !im_warp || !grad_loss || !grad_warp) return CERB_EINVAL;
     return census_backward(im, im_warp, grad_loss, grad_warp, B, H, W, max_distance, static_cast<hipStream_t>(stream));
+}
+
+// the occlusion ops: (B,2,H,W) fp32 in, (B,1,H,W) fp32 out.  2 * H * W < 2^31 is what keeps the splat's 64-bit fixed-point sum
+// from wrapping (occlusion.hip), H, W <= 2^24 keeps floor(x) + 1 exact in fp32 wherever a tap counts.
+static int occlusion_args_ok(int B, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B <= 0 || H <= 0 || W <= 0) return CERB_EINVAL;
+    if (H > (1 << 24) || W > (1 << 24)) return CERB_ETOOLARGE;
+    const int64_t tiles = (static_cast<int64_t>(W) + 63) / 64 * ((static_cast<int64_t>(H) + 15) / 16) * B;
+    const int64_t blocks = (static_cast<int64_t>(B) * H * W + 255) / 256;
+    return loss_size_ok(B, 2, H, W, tiles > blocks ? tiles : blocks);
+}
+
+int64_t cerberus_corresponding_map_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return corresponding_map_workspace_bytes(B, H, W);
+}
+
+int cerberus_corresponding_map(const void *data, void *map, void *workspace, int64_t workspace_bytes, int B, int H, int W,
+                               int is_flow, int dtype, void *stream) {
+    const int rc = occlusion_args_ok(B, H, W, dtype);
+    if (rc) return rc;
+    if (!data || !map || !workspace) return CERB_EINVAL;
+    if (is_flow != 0 && is_flow != 1) return CERB_EINVAL;
+    if (workspace_bytes < corresponding_map_workspace_bytes(B, H, W)) return CERB_EINVAL;
+    return corresponding_map(data, map, workspace, B, H, W, is_flow, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_occlusion_mask_bidirection(const void *flow12, const void *flow21, void *mask, int B, int H, int W, float scale,
+                                        float bias, int dtype, void *stream) {
+    const int rc = occlusion_args_ok(B, H, W, dtype);
+    if (rc) return rc;
+    if (!flow12 || !flow21 || !mask) return CERB_EINVAL;
+    return occlusion_mask_bidirection(flow12, flow21, mask, B, H, W, scale, bias, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

@@ -230,6 +230,13 @@ int census_forward(const void *im, const void *im_warp, void *loss, void *worksp
 int census_backward(const void *im, const void *im_warp, const void *grad_loss, void *grad_warp, int B, int H, int W,
                     int max_distance, hipStream_t s);
 
+// occlusion.hip: unFlowLoss's occlusion masks, fp32, forward only; arguments are checked by api.hip.  `workspace`: one 64-bit
+// fixed-point accumulator per pixel of the map, zeroed on the stream by the call itself.
+int64_t corresponding_map_workspace_bytes(int B, int H, int W);
+int corresponding_map(const void *data, void *map, void *workspace, int B, int H, int W, int is_flow, hipStream_t s);
+int occlusion_mask_bidirection(const void *flow12, const void *flow21, void *mask, int B, int H, int W, float scale, float bias,
+                               hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

@@ -9,13 +9,20 @@ Gradients flow to both the image and the flow.
 
 ``mesh_grid`` / ``norm_grid`` (:11-32) are kept for importers; they are not on
 the hot path any more.
+
+The occlusion handling of the reference -- ``get_corresponding_map`` (:34-81), ``get_occu_mask_backward`` (:108-117),
+``get_occu_mask_bidirection`` (:96-106), the masked ``loss_photometric`` (:225-241) and the mask schedule of ``forward``
+(:286-295) -- is here under the same names: fp32 CUDA tensors take the HIP ops of ``csrc/occlusion.hip`` (a bit-reproducible
+splat, a one-launch bidirectional check), everything else a stock-op formulation; ``unFlowLoss(occlusion=True)`` switches
+the schedule on.
 """
 import torch
 
 from .. import ops as _ops
 
 __all__ = ["flow_warp", "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness",
-           "TernaryLoss", "census_loss", "unFlowLoss"]
+           "TernaryLoss", "census_loss", "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection",
+           "unFlowLoss"]
 
 
 def area_resize(image, size):
@@ -31,10 +38,10 @@ def area_pyramid(image, sizes):
     return list(torch.ops.cerberus.area_pyramid(image, flat))
 
 
-def mesh_grid(batch_sz, height, width):
-    """Pixel-coordinate grid, (B,2,H,W), channel 0 = x, channel 1 = y."""
-    xs = torch.arange(0, width).view(1, 1, width).expand(batch_sz, height, width)
-    ys = torch.arange(0, height).view(1, height, 1).expand(batch_sz, height, width)
+def mesh_grid(batch_sz, height, width, device=None):
+    """Pixel-coordinate grid, (B,2,H,W), channel 0 = x, channel 1 = y (``device``: where to build it; default CPU)."""
+    xs = torch.arange(0, width, device=device).view(1, 1, width).expand(batch_sz, height, width)
+    ys = torch.arange(0, height, device=device).view(1, height, 1).expand(batch_sz, height, width)
     return torch.stack([xs, ys], 1)
 
 
@@ -130,7 +137,7 @@ def _edge_aware_smoothness(flow, image, alpha, degree):
 
 
 def _photometric_stock(im_orig, im_recons, l1_weight, ssim_weight):
-    """The photometric term in stock ops (``loss_photometric`` below, all-ones mask); a weight of None or 0 skips its term."""
+    """The photometric term in stock ops (``loss_photometric`` below without a mask); a weight of None or 0 skips its term."""
     terms = []
     if l1_weight:
         terms.append(l1_weight * (im_orig - im_recons).abs())
@@ -149,10 +156,11 @@ def _fusable(a, b):
 
 def photometric_loss(im_orig, im_recons, l1_weight=0.15, ssim_weight=0.85):
     """mean(l1_weight * |im_orig - im_recons| + ssim_weight * clamp((1 - SSIM(im_recons, im_orig)) / 2, 0, 1)) as a 0-dim
-    tensor: ``unFlowLoss.loss_photometric`` (reference :236-255, all-ones mask) as ONE fused HIP forward and one fused
+    tensor: ``unFlowLoss.loss_photometric`` (reference :225-241) without a mask as ONE fused HIP forward and one fused
     backward (``cerberus::photometric_loss``), differentiable in both images, reductions in a fixed order without
     atomics.  A weight of None or 0 skips its term.  fp32 CUDA tensors with H, W >= 2 take the HIP op; anything else
-    (16-bit tensors, CPU tensors) the stock-op formulation."""
+    (16-bit tensors, CPU tensors) the stock-op formulation.  An occlusion mask is applied by the caller:
+    ``photometric_loss(im_orig * m, im_recons * m, ...) / m.mean()`` is the masked term for a 0 / 1 mask ``m``."""
     l1_weight, ssim_weight = float(l1_weight or 0.0), float(ssim_weight or 0.0)
     if (_fusable(im_orig, im_recons) and im_orig.shape == im_recons.shape and min(im_orig.shape[2:]) >= 2
             and (l1_weight or ssim_weight)):
@@ -174,7 +182,7 @@ def edge_smoothness(flow, image, alpha, degree):
 
 def census_loss(im, im_warp, max_distance=1):
     """``TernaryLoss(im, im_warp, max_distance).mean()`` as a 0-dim tensor: the census term of ``loss_photometric``
-    (reference :237-239, all-ones mask) as ONE fused HIP forward and one fused backward (``cerberus::census_loss``),
+    (reference :237-239; a mask multiplies both images before the call) as ONE fused HIP forward and one fused backward (``cerberus::census_loss``),
     differentiable in both images, reduced in a fixed order without atomics.  fp32 CUDA tensors of equal shape with 3
     channels, ``max_distance`` 1, 2 or 3 and H, W >= 2 * max_distance + 1 take the HIP op; anything else (16-bit or CPU
     tensors, other windows) the stock-op formulation."""
@@ -184,13 +192,102 @@ def census_loss(im, im_warp, max_distance=1):
     return TernaryLoss(im, im_warp, max_distance).mean()
 
 
+# ---- occlusion masks (reference :34-81, :96-117) ---------------------------------------------------------------------
+def _corresponding_map_stock(data):
+    """``get_corresponding_map`` in stock ops, differentiable through the weights: every source pixel adds
+    ``(1 - |x - xt|)(1 - |y - yt|)`` to the taps ``floor`` / ``floor + 1`` of its target ``(x, y)``; a tap outside the map is
+    dropped, judged on the unclamped integer.  Taps are added in the reference's order (both ``+ 1``, then x ``+ 1``, then y
+    ``+ 1``, then both ``floor``) by one ``scatter_add_``.  A non-finite target adds nothing."""
+    B, _, H, W = data.shape
+    x, y = data[:, 0].reshape(B, -1), data[:, 1].reshape(B, -1)
+    x1, y1 = torch.floor(x), torch.floor(y)
+    index, values = [], []
+    for xt, yt in ((x1 + 1, y1 + 1), (x1 + 1, y1), (x1, y1 + 1), (x1, y1)):
+        inside = (xt >= 0) & (xt <= W - 1) & (yt >= 0) & (yt <= H - 1)          # False for NaN and +-Inf
+        weight = (1 - torch.abs(x - xt)) * (1 - torch.abs(y - yt))
+        values.append(torch.where(inside, weight, torch.zeros_like(weight)))
+        zero = torch.zeros_like(xt)
+        index.append(torch.where(inside, xt, zero).long() + torch.where(inside, yt, zero).long() * W)
+    out = torch.zeros(B, H * W, dtype=data.dtype, device=data.device)
+    out = out.scatter_add(1, torch.cat(index, 1), torch.cat(values, 1))
+    return out.view(B, 1, H, W)
+
+
+def _flow_fusable(flow):
+    """What the occlusion ops take: one fp32 (B,2,H,W) tensor on a GPU."""
+    return _fusable(flow, flow) and flow.shape[1] == 2
+
+
+def get_corresponding_map(data):
+    """
+    :param data: unnormalized coordinates Bx2xHxW
+    :return: Bx1xHxW
+
+    How many source pixels land on every pixel: the bilinear forward splat of ones (reference :34-81).  fp32 CUDA
+    coordinates that carry no gradient take ``cerberus::corresponding_map`` (64-bit fixed-point sums: the same bits on
+    every run); anything else -- CPU or 16-bit tensors, coordinates that require grad (the map is differentiable through
+    its weights) -- the stock-op formulation."""
+    if _flow_fusable(data) and not (torch.is_grad_enabled() and data.requires_grad):
+        return torch.ops.cerberus.corresponding_map(data, False)
+    return _corresponding_map_stock(data)
+
+
+def _occu_mask_backward_stock(flow21, theta):
+    B, _, H, W = flow21.shape
+    base_grid = mesh_grid(B, H, W, device=flow21.device).type_as(flow21)
+    corr_map = _corresponding_map_stock(base_grid + flow21)
+    return (corr_map.clamp(min=0., max=1.) < theta).float()
+
+
+def get_occu_mask_backward(flow21, theta=0.2):
+    '''
+    Get an occlusion mask using backward propagation: 1 where fewer than ``theta`` pixels of the other frame land
+    (reference :108-117).  A constant: no gradient reaches the flow.  fp32 CUDA flows take ``cerberus::corresponding_map``
+    (which forms pixel + flow itself) and one comparison; anything else the stock-op formulation.
+    '''
+    flow21 = flow21.detach()
+    if _flow_fusable(flow21):
+        corr_map = torch.ops.cerberus.corresponding_map(flow21, True)
+        return (corr_map.clamp(min=0., max=1.) < theta).float()
+    return _occu_mask_backward_stock(flow21, theta)
+
+
+def _occu_mask_bidirection_stock(flow12, flow21, scale, bias):
+    import torch.nn.functional as F
+    b, _, h, w = flow12.shape
+    grid = norm_grid(mesh_grid(b, h, w, device=flow12.device).type_as(flow12) + flow12)
+    warped = F.grid_sample(flow21, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+    diff = flow12 + warped
+    mag = (flow12 * flow12).sum(1, keepdim=True) + (warped * warped).sum(1, keepdim=True)
+    return ((diff * diff).sum(1, keepdim=True) > scale * mag + bias).float()
+
+
+def get_occu_mask_bidirection(flow12, flow21, scale=0.01, bias=0.5):
+    '''
+    Get an occlusion mask using both flows such that they match each other: 1 where
+    ``|flow12 + warp(flow21)|^2 > scale (|flow12|^2 + |warp(flow21)|^2) + bias`` (reference :96-106).  A constant: no
+    gradient reaches either flow.  fp32 CUDA flows of equal shape take ``cerberus::occlusion_mask_bidirection`` (one
+    launch, the warped flow is never written); anything else the stock-op formulation.
+    '''
+    flow12, flow21 = flow12.detach(), flow21.detach()
+    if _flow_fusable(flow12) and _flow_fusable(flow21) and flow12.shape == flow21.shape and flow12.device == flow21.device:
+        return torch.ops.cerberus.occlusion_mask_bidirection(flow12, flow21, float(scale), float(bias))
+    return _occu_mask_bidirection_stock(flow12, flow21, scale, bias)
+
+
 class unFlowLoss(torch.nn.Module):
     """Counterpart of ``unFlowLoss`` (:189-322) for the terms the Cerberus configs use: L1 and SSIM
     photometric terms on the image pair warped by the predicted flow at every pyramid scale,
     edge-aware smoothness, forward / backward consistency.  Same constructor keywords, same
     ``forward(predictions, targets)`` with ``predictions['flow'|'flow_b']`` (lists, full resolution
-    first) and ``targets['l_img'|'l_seq']``.  The occlusion masks (dead code in the reference, :285-297: the mask is
-    all ones) are not built.
+    first) and ``targets['l_img'|'l_seq']``.
+
+    ``occlusion=True`` (opt-in) runs the mask schedule the reference carries commented out (:286-295): at the first used
+    scale ``occlusion_masks(flow12, flow21)`` -- ``1 - get_occu_mask_backward`` of the opposite flow when
+    ``back_occ_only`` else ``1 - get_occu_mask_bidirection``, argument order as upstream --, at every further used scale the
+    previous scale's masks resized with ``nearest``; each photometric term is then the masked one of ``loss_photometric``.
+    Masks are constants (no gradient flows through them); override ``occlusion_masks`` for masks of your own.  The default
+    ``False`` builds no mask and keeps every result as it was.
 
     ``weights`` may carry ``"ternary"``, the census term (``TernaryLoss`` above, added to the photometric term as in the
     reference, :237-239), with ``fused=True`` (``census_loss``, the HIP op) or ``backend='torch'`` (stock ops).  With the
@@ -205,7 +302,7 @@ class unFlowLoss(torch.nn.Module):
     result as it was."""
 
     def __init__(self, weight=1.0, weights=None, consistency=True, back_occ_only=False,
-                 backend="hip", fused=False, **kwargs):
+                 backend="hip", fused=False, occlusion=False, **kwargs):
         super().__init__()
         weights = weights or {"l1": 0.15, "ssim": 0.85}
         if backend not in ("hip", "torch"):
@@ -226,6 +323,7 @@ class unFlowLoss(torch.nn.Module):
             raise ValueError("fused=True needs backend='hip' (the fused terms are HIP ops)")
         self.backend = backend
         self.fused = bool(fused)
+        self.occlusion = bool(occlusion)
 
     def _fused(self):
         # `backend` may be reassigned on a live object: fused has no effect unless the backend is 'hip' at call time
@@ -240,7 +338,52 @@ class unFlowLoss(torch.nn.Module):
         return flow_warp(image, flow, pad="border") if self.backend == "hip" \
             else _torch_flow_warp(image, flow, pad="border")
 
-    def loss_photometric(self, im_orig, im_recons):
+    def occlusion_masks(self, flow12, flow21):
+        """The non-occluded masks ``(mask1, mask2)`` (1 = visible, (B,1,H,W)) of the two photometric terms, from the flows of
+        the first used scale (reference :286-292).  ``backend='hip'``: the public functions above (HIP ops for fp32 CUDA
+        flows); ``'torch'``: their stock formulations."""
+        f12, f21 = flow12.detach(), flow21.detach()
+        if self.backend == "hip":
+            backward, bidirection = get_occu_mask_backward, get_occu_mask_bidirection
+        else:
+            backward = lambda f: _occu_mask_backward_stock(f, 0.2)
+            bidirection = lambda a, b: _occu_mask_bidirection_stock(a, b, 0.01, 0.5)
+        if self.back_occ_only:
+            return 1 - backward(f21), 1 - backward(f12)
+        return 1 - bidirection(f12, f21), 1 - bidirection(f21, f12)
+
+    def _loss_photometric_masked(self, im_orig, im_recons, occu_mask):
+        """Reference :225-241: every term masked, the sum of the means over the mask's mean; an all-zero mask counts as
+        all ones.  That rule is applied on the device (no host comparison: the step stays capturable)."""
+        occu_mask = occu_mask.detach()
+        mean = occu_mask.mean()
+        empty = mean == 0
+        occu_mask = torch.where(empty, torch.ones_like(occu_mask), occu_mask)
+        mean = torch.where(empty, torch.ones_like(mean), mean)
+        if self._fused():
+            # for a 0 / 1 mask |a m - b m| and |a - b| m are the same floats: the fused ops serve unchanged
+            orig_m, recons_m = im_orig * occu_mask, im_recons * occu_mask
+            loss = photometric_loss(orig_m, recons_m, self.l1_weight, self.ssim_weight)
+            if self.ternary_weight is not None:
+                census = self.ternary_weight * census_loss(recons_m, orig_m)
+                loss = loss + census if (self.l1_weight or self.ssim_weight) else census
+            return loss / mean
+        terms = []
+        if self.l1_weight is not None:
+            terms.append(self.l1_weight * (im_orig - im_recons).abs() * occu_mask)
+        if self.ssim_weight is not None:
+            terms.append(self.ssim_weight * _ssim_distance(im_recons * occu_mask, im_orig * occu_mask))
+        if self.ternary_weight is not None:
+            if self.backend != "torch":        # `backend` may be reassigned on a live object
+                raise NotImplementedError("the census (ternary) term needs fused=True or backend='torch'")
+            terms.append(self.ternary_weight * TernaryLoss(im_recons * occu_mask, im_orig * occu_mask))
+        return sum(t.mean() for t in terms) / mean
+
+    def loss_photometric(self, im_orig, im_recons, occu_mask=None):
+        """The photometric term of one direction at one scale.  ``occu_mask`` (B,1,H,W) or (B,C,H,W), 1 = visible: the
+        masked term of the reference (:225-241); ``None``: the unmasked term (the reference's all-ones mask)."""
+        if occu_mask is not None:
+            return self._loss_photometric_masked(im_orig, im_recons, occu_mask)
         if self._fused():
             loss = photometric_loss(im_orig, im_recons, self.l1_weight, self.ssim_weight)
             if self.ternary_weight is not None:
@@ -257,7 +400,7 @@ class unFlowLoss(torch.nn.Module):
             if self.backend != "torch":        # `backend` may be reassigned on a live object
                 raise NotImplementedError("the census (ternary) term needs fused=True or backend='torch'")
             terms.append(self.ternary_weight * TernaryLoss(im_recons, im_orig))
-        return sum(t.mean() for t in terms)          # (/ mean of the all-ones mask = 1)
+        return sum(t.mean() for t in terms)          # (no mask: the reference divides by the mean of ones)
 
     def loss_smooth(self, flow, image):
         fn = edge_smoothness if self._fused() else _edge_aware_smoothness
@@ -271,6 +414,7 @@ class unFlowLoss(torch.nn.Module):
         # F.interpolate per scale and image, :279-280)
         pyr1 = dict(zip(used, self._pyramid(targets["l_img"], sizes)))
         pyr2 = dict(zip(used, self._pyramid(targets["l_seq"], sizes)))
+        mask1 = mask2 = None
         for i, (f12, f21) in enumerate(zip(predictions["flow"], predictions["flow_b"])):
             if self.w_wrp_scales[i] == 0:
                 continue
@@ -278,10 +422,16 @@ class unFlowLoss(torch.nn.Module):
             im1, im2 = pyr1[i], pyr2[i]
             if i == 0:
                 s = min(size)
-            warp = self.loss_photometric(im1, self._warp(im2, f12))
+            if self.occlusion:
+                if mask1 is None:
+                    mask1, mask2 = self.occlusion_masks(f12, f21)
+                else:
+                    mask1 = torch.nn.functional.interpolate(mask1, size, mode="nearest")
+                    mask2 = torch.nn.functional.interpolate(mask2, size, mode="nearest")
+            warp = self.loss_photometric(im1, self._warp(im2, f12), mask1)
             smooth = self.loss_smooth(f12 / s, im1)
             if self.consistency:
-                warp = (warp + self.loss_photometric(im2, self._warp(im1, f21))) / 2.
+                warp = (warp + self.loss_photometric(im2, self._warp(im1, f21), mask2)) / 2.
                 smooth = (smooth + self.loss_smooth(f21 / s, im2)) / 2.
             total_warp = total_warp + warp * self.w_wrp_scales[i]
             total_smooth = total_smooth + smooth * self.w_sm_scales[i]

@@ -1,5 +1,5 @@
-from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, mesh_grid, norm_grid, photometric_loss,
-                         unFlowLoss)
+from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, get_corresponding_map, get_occu_mask_backward,
+                         get_occu_mask_bidirection, mesh_grid, norm_grid, photometric_loss, unFlowLoss)
 
 __all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoothness", "TernaryLoss", "census_loss",
-           "unFlowLoss"]
+           "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "unFlowLoss"]

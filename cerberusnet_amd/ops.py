@@ -64,6 +64,8 @@ _def.define("photometric_loss_backward(Tensor im_orig, Tensor im_recons, Tensor 
 _def.define("census_loss(Tensor im, Tensor im_warp, int max_distance) -> Tensor")
 _def.define("census_loss_backward(Tensor im, Tensor im_warp, Tensor grad_loss, int max_distance, bool need_im, "
             "bool need_warp) -> (Tensor, Tensor)")
+_def.define("corresponding_map(Tensor data, bool is_flow) -> Tensor")
+_def.define("occlusion_mask_bidirection(Tensor flow12, Tensor flow21, float scale, float bias) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -747,6 +749,63 @@ def _census_loss_backward_meta(im, im_warp, grad_loss, max_distance, need_im, ne
             torch.empty_like(im_warp) if need_warp else im_warp.new_empty((0,)))
 
 
+# the occlusion masks (UnFlowLoss.py:34-81, :96-117), csrc/occlusion.hip: forward only
+def _corresponding_map_workspace_bytes(B, H, W):
+    """cerberus_corresponding_map_workspace_bytes in pure Python (a test holds the two equal): one 64-bit fixed-point
+    accumulator per pixel of the map."""
+    if B <= 0 or H <= 0 or W <= 0:
+        return 0
+    return 8 * B * H * W
+
+
+def _occlusion_check(t, name, what):
+    if t.dim() != 4 or t.shape[1] != 2:
+        raise RuntimeError("%s: %s must be a (B,2,H,W) tensor, got %s" % (what, name, tuple(t.shape)))
+    if t.dtype != torch.float32:
+        raise RuntimeError("%s: %s must be float32, got %s (16-bit tensors take the stock-op path of the wrappers in "
+                           "loss_functions.UnFlowLoss)" % (what, name, t.dtype))
+    if t.numel() == 0:
+        raise RuntimeError("%s: %s has no pixels: %s" % (what, name, tuple(t.shape)))
+
+
+def _corresponding_map_cuda(data, is_flow):
+    what = "cerberus::corresponding_map"
+    _occlusion_check(data, "data", what)
+    x = data.contiguous()
+    B, _, H, W = x.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_corresponding_map_workspace_bytes(B, H, W)
+    ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.int64, device=x.device)      # zeroed on the stream by the library
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.cerberus_corresponding_map(x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws_bytes, B, H, W, int(bool(is_flow)),
+                                            0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return out
+
+
+def _occlusion_mask_bidirection_cuda(flow12, flow21, scale, bias):
+    what = "cerberus::occlusion_mask_bidirection"
+    _occlusion_check(flow12, "flow12", what)
+    _occlusion_check(flow21, "flow21", what)
+    if flow12.shape != flow21.shape:
+        raise RuntimeError("%s: flow shapes differ: %s vs %s" % (what, tuple(flow12.shape), tuple(flow21.shape)))
+    if flow12.device != flow21.device:
+        raise RuntimeError("%s: inputs on different devices: %s vs %s" % (what, flow12.device, flow21.device))
+    a, b = flow12.contiguous(), flow21.contiguous()
+    B, _, H, W = a.shape
+    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = _lib.get().cerberus_occlusion_mask_bidirection(a.data_ptr(), b.data_ptr(), out.data_ptr(), B, H, W, float(scale),
+                                                            float(bias), 0, _stream_ptr(a))
+    _lib.check(rc, what)
+    return out
+
+
+def _occlusion_meta(t, *_):
+    return t.new_empty((t.shape[0], 1, t.shape[2], t.shape[3]), dtype=torch.float32)
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -778,6 +837,12 @@ _def.impl("census_loss", _no_cpu("census_loss"), "CPU")
 _def.impl("census_loss_backward", _census_loss_backward_cuda, "CUDA")
 _def.impl("census_loss_backward", _census_loss_backward_meta, "Meta")
 _def.impl("census_loss_backward", _no_cpu("census_loss_backward"), "CPU")
+_def.impl("corresponding_map", _corresponding_map_cuda, "CUDA")
+_def.impl("corresponding_map", _occlusion_meta, "Meta")
+_def.impl("corresponding_map", _no_cpu("corresponding_map"), "CPU")
+_def.impl("occlusion_mask_bidirection", _occlusion_mask_bidirection_cuda, "CUDA")
+_def.impl("occlusion_mask_bidirection", _occlusion_meta, "Meta")
+_def.impl("occlusion_mask_bidirection", _no_cpu("occlusion_mask_bidirection"), "CPU")
 _def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
 _def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
 _def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
@@ -936,6 +1001,16 @@ def _area_resize_backward(ctx, grad):
 torch.library.register_autograd("cerberus::area_resize", _area_resize_backward,
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::area_pyramid", _area_resize_backward,
+                                setup_context=lambda ctx, inputs, output: None)
+def _occlusion_backward(ctx, grad):
+    raise RuntimeError("the cerberus:: occlusion ops are not differentiable: a mask is a constant of the loss (the reference "
+                       "builds it with a comparison, UnFlowLoss.py:105, :116); for a map that is differentiable through "
+                       "its weights call loss_functions.get_corresponding_map on a tensor that requires grad")
+
+
+torch.library.register_autograd("cerberus::corresponding_map", _occlusion_backward,
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::occlusion_mask_bidirection", _occlusion_backward,
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::flow_upsample", _upsample_backward,
                                 setup_context=_upsample_setup)

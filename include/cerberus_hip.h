@@ -321,6 +321,37 @@ int cerberus_census_loss_backward(const void *im, const void *im_warp, const voi
                                   void *grad_warp, int B, int H, int W, int max_distance, int dtype,
                                   void *stream);
 
+/* unFlowLoss's occlusion masks (additions only: no ABI bump): forward-only ops, fp32, no gradient of any kind (the masks
+ * are constants of the loss).
+ *
+ * cerberus_corresponding_map: get_corresponding_map (UnFlowLoss.py:34-81), the bilinear forward splat of ones.
+ *   data : (B,2,H,W) fp32.  is_flow = 0: absolute target coordinates (channel 0 = x, 1 = y), the reference's argument;
+ *          is_flow = 1: a flow; the target is pixel + flow, formed in fp32 by the kernel (get_occu_mask_backward, :108-117)
+ *   map  : (B,1,H,W) fp32, overwritten: for every source pixel the taps floor / floor + 1 of its target (x, y) receive
+ *          (1 - |x - xt|)(1 - |y - yt|); a tap outside the map is dropped, judged on the unclamped integer.
+ *   workspace : cerberus_corresponding_map_workspace_bytes(B,H,W) = 8 B H W bytes (0 for a non-positive size), zeroed on
+ *          the stream by the call itself (a kernel: capturable, no host synchronisation).
+ * Sums are 64-bit integers of weights scaled by the constant 2^33 and rounded (a weight lies in [0, 1]; at most 2^-34
+ * per tap, nothing for weights >= 2^-10): integer adds commute, so two runs give the same bits, eager or replayed from a
+ * graph; there are no floating-point atomics.  A pixel that receives every source holds less than H*W * 2^33 < 2^63: no
+ * wrap (H*W < 2^30 is enforced).  NaN and +-Inf positions contribute nothing (in the reference +-Inf contributes nothing and NaN is undefined
+ * behaviour); positions of any magnitude are dropped by a range test in fp32 before any index is formed.
+ *
+ * cerberus_occlusion_mask_bidirection: get_occu_mask_bidirection (:96-106) in one launch.
+ *   flow12, flow21 : (B,2,H,W) fp32;  mask : (B,1,H,W) fp32 of 0 / 1, overwritten
+ *   w = flow21 sampled where cerberus_flow_warp_forward(flow21, flow12, CERB_PAD_ZEROS, CERB_INTERP_BILINEAR) samples it
+ *   (the same bits; the warped flow is never written);  mask = |flow12 + w|^2 > scale (|flow12|^2 + |w|^2) + bias.
+ *   An IEEE comparison: a NaN in any of a pixel's terms gives 0 there.
+ *
+ * Errors (both): unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B, H or W <= 0, a null pointer, an
+ * is_flow other than 0 / 1, a workspace that is too small CERB_EINVAL; H or W > 2^24 or 2*H*W >= 2^31 CERB_ETOOLARGE --
+ * all before any launch. */
+int64_t cerberus_corresponding_map_workspace_bytes(int B, int H, int W);
+int cerberus_corresponding_map(const void *data, void *map, void *workspace, int64_t workspace_bytes,
+                               int B, int H, int W, int is_flow, int dtype, void *stream);
+int cerberus_occlusion_mask_bidirection(const void *flow12, const void *flow21, void *mask, int B, int H,
+                                        int W, float scale, float bias, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
