@@ -51,6 +51,8 @@ PROTOTYPES = {
     "cerberus_corresponding_map_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_corresponding_map": (_I, [_P, _P, _P, _I64] + [_I] * 5 + [_P]),
     "cerberus_occlusion_mask_bidirection": (_I, [_P, _P, _P] + [_I] * 3 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_reproject_warp_forward": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float, _I, _P]),
+    "cerberus_reproject_warp_backward": (_I, [_P] * 6 + [_I] * 4 + [ctypes.c_float, _I, _P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
-// census.hip and occlusion.hip.
+// census.hip, occlusion.hip and reproject.hip.
 #include <atomic>
 #include <cstring>
 
@@ -409,6 +409,33 @@ int cerberus_occlusion_mask_bidirection(const void *flow12, const void *flow21, 
     if (rc) return rc;
     if (!flow12 || !flow21 || !mask) return CERB_EINVAL;
     return occlusion_mask_bidirection(flow12, flow21, mask, B, H, W, scale, bias, static_cast<hipStream_t>(stream));
+}
+
+// the reprojection warp: image (B,C,H,W), depth (B,1,H,W), fp32.  The reference divides by W - 1 and H - 1; the whole image
+// tensor is addressed with one 31-bit element count.
+static int reproject_args_ok(int B, int C, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B <= 0 || C <= 0 || H < 2 || W < 2) return CERB_EINVAL;
+    if (static_cast<int64_t>(B) * C * H * W > 0x7fffffff) return CERB_EINVAL;
+    return CERB_OK;
+}
+
+int cerberus_reproject_warp_forward(const void *image, const void *depth, const void *inv_K, const void *proj, void *out, int B,
+                                    int C, int H, int W, float eps, int dtype, void *stream) {
+    const int rc = reproject_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (!image || !depth || !inv_K || !proj || !out) return CERB_EINVAL;
+    return reproject_warp_forward(image, depth, inv_K, proj, out, B, C, H, W, eps, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_reproject_warp_backward(const void *image, const void *depth, const void *inv_K, const void *proj, const void *grad_out,
+                                     void *grad_depth, int B, int C, int H, int W, float eps, int dtype, void *stream) {
+    const int rc = reproject_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (!image || !depth || !inv_K || !proj || !grad_out || !grad_depth) return CERB_EINVAL;
+    return reproject_warp_backward(image, depth, inv_K, proj, grad_out, grad_depth, B, C, H, W, eps,
+                                   static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

@@ -237,6 +237,13 @@ int corresponding_map(const void *data, void *map, void *workspace, int B, int H
 int occlusion_mask_bidirection(const void *flow12, const void *flow21, void *mask, int B, int H, int W, float scale, float bias,
                                hipStream_t s);
 
+// reproject.hip: the stereo reprojection warp of the depth reconstruction loss, fp32; arguments are checked by api.hip.
+// inv_k: (B,3,3), proj: (B,3,4), both in device memory.
+int reproject_warp_forward(const void *image, const void *depth, const void *inv_k, const void *proj, void *out, int B, int C, int H,
+                           int W, float eps, hipStream_t s);
+int reproject_warp_backward(const void *image, const void *depth, const void *inv_k, const void *proj, const void *grad_out,
+                            void *grad_depth, int B, int C, int H, int W, float eps, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

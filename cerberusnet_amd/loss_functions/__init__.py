@@ -1,5 +1,7 @@
+from .depth_losses import BackprojectDepth, DepthReconstructionLossV1, Project3D, reproject_warp
 from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, get_corresponding_map, get_occu_mask_backward,
                          get_occu_mask_bidirection, mesh_grid, norm_grid, photometric_loss, unFlowLoss)
 
 __all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoothness", "TernaryLoss", "census_loss",
-           "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "unFlowLoss"]
+           "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "unFlowLoss",
+           "BackprojectDepth", "Project3D", "DepthReconstructionLossV1", "reproject_warp"]

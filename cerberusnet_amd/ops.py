@@ -66,6 +66,8 @@ _def.define("census_loss_backward(Tensor im, Tensor im_warp, Tensor grad_loss, i
             "bool need_warp) -> (Tensor, Tensor)")
 _def.define("corresponding_map(Tensor data, bool is_flow) -> Tensor")
 _def.define("occlusion_mask_bidirection(Tensor flow12, Tensor flow21, float scale, float bias) -> Tensor")
+_def.define("reproject_warp(Tensor image, Tensor depth, Tensor inv_K, Tensor proj, float eps) -> Tensor")
+_def.define("reproject_warp_backward(Tensor image, Tensor depth, Tensor inv_K, Tensor proj, Tensor grad_out, float eps) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -806,6 +808,61 @@ def _occlusion_meta(t, *_):
     return t.new_empty((t.shape[0], 1, t.shape[2], t.shape[3]), dtype=torch.float32)
 
 
+# the stereo reprojection warp of the depth reconstruction loss (depth_losses.py:112-206), csrc/reproject.hip
+def _reproject_check(image, depth, inv_K, proj, what, grad_out=None):
+    named = [("image", image), ("depth", depth), ("inv_K", inv_K), ("proj", proj)]
+    if grad_out is not None:
+        named.append(("grad_out", grad_out))
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s must be float32, got %s (16-bit tensors take the stock-op path of "
+                               "loss_functions.reproject_warp)" % (what, name, t.dtype))
+        if t.device != image.device:
+            raise RuntimeError("%s: inputs on different devices: image on %s, %s on %s" % (what, image.device, name, t.device))
+    if image.dim() != 4 or image.numel() == 0:
+        raise RuntimeError("%s: image must be a non-empty 4-D NCHW tensor, got %s" % (what, tuple(image.shape)))
+    B, C, H, W = image.shape
+    if tuple(depth.shape) != (B, 1, H, W):
+        raise RuntimeError("%s: depth must be %s for an image of %s, got %s" % (what, (B, 1, H, W), tuple(image.shape),
+                                                                               tuple(depth.shape)))
+    if tuple(inv_K.shape) != (B, 3, 3):
+        raise RuntimeError("%s: inv_K must be %s (the upper-left 3 x 3 of the inverse intrinsics), got %s"
+                           % (what, (B, 3, 3), tuple(inv_K.shape)))
+    if tuple(proj.shape) != (B, 3, 4):
+        raise RuntimeError("%s: proj must be %s ((K @ T)[:, :3, :]), got %s" % (what, (B, 3, 4), tuple(proj.shape)))
+    if grad_out is not None and grad_out.shape != image.shape:
+        raise RuntimeError("%s: grad_out %s does not match the image %s" % (what, tuple(grad_out.shape), tuple(image.shape)))
+    if H < 2 or W < 2:
+        raise RuntimeError("%s: H and W must be at least 2 (positions are normalised by W - 1 and H - 1), got %s"
+                           % (what, tuple(image.shape)))
+
+
+def _reproject_warp_cuda(image, depth, inv_K, proj, eps):
+    what = "cerberus::reproject_warp"
+    _reproject_check(image, depth, inv_K, proj, what)
+    img, d, k, p = image.contiguous(), depth.contiguous(), inv_K.contiguous(), proj.contiguous()
+    B, C, H, W = img.shape
+    out = torch.empty_like(img)
+    with torch.cuda.device(img.device):
+        rc = _lib.get().cerberus_reproject_warp_forward(img.data_ptr(), d.data_ptr(), k.data_ptr(), p.data_ptr(), out.data_ptr(),
+                                                        B, C, H, W, float(eps), 0, _stream_ptr(img))
+    _lib.check(rc, what)
+    return out
+
+
+def _reproject_warp_backward_cuda(image, depth, inv_K, proj, grad_out, eps):
+    what = "cerberus::reproject_warp_backward"
+    _reproject_check(image, depth, inv_K, proj, what, grad_out)
+    img, d, k, p, g = (t.contiguous() for t in (image, depth, inv_K, proj, grad_out))
+    B, C, H, W = img.shape
+    grad = torch.empty_like(d)
+    with torch.cuda.device(img.device):
+        rc = _lib.get().cerberus_reproject_warp_backward(img.data_ptr(), d.data_ptr(), k.data_ptr(), p.data_ptr(), g.data_ptr(),
+                                                         grad.data_ptr(), B, C, H, W, float(eps), 0, _stream_ptr(img))
+    _lib.check(rc, what)
+    return grad
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -843,6 +900,12 @@ _def.impl("corresponding_map", _no_cpu("corresponding_map"), "CPU")
 _def.impl("occlusion_mask_bidirection", _occlusion_mask_bidirection_cuda, "CUDA")
 _def.impl("occlusion_mask_bidirection", _occlusion_meta, "Meta")
 _def.impl("occlusion_mask_bidirection", _no_cpu("occlusion_mask_bidirection"), "CPU")
+_def.impl("reproject_warp", _reproject_warp_cuda, "CUDA")
+_def.impl("reproject_warp", lambda image, depth, k, p, eps: image.new_empty(image.shape), "Meta")
+_def.impl("reproject_warp", _no_cpu("reproject_warp"), "CPU")
+_def.impl("reproject_warp_backward", _reproject_warp_backward_cuda, "CUDA")
+_def.impl("reproject_warp_backward", lambda image, depth, k, p, g, eps: depth.new_empty(depth.shape), "Meta")
+_def.impl("reproject_warp_backward", _no_cpu("reproject_warp_backward"), "CPU")
 _def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
 _def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
 _def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
@@ -1064,6 +1127,22 @@ def _smoothness_backward(ctx, grad):
     return gf, None, None, None
 
 
+def _reproject_setup(ctx, inputs, output):
+    image, depth, inv_K, proj, eps = inputs
+    ctx.save_for_backward(image, depth, inv_K, proj)      # nothing but the inputs: the backward recomputes the positions
+    ctx.eps = eps
+
+
+def _reproject_backward(ctx, grad):
+    image, depth, inv_K, proj = ctx.saved_tensors
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+        raise RuntimeError("cerberus::reproject_warp has a gradient for the depth only (the image is a target, the camera "
+                           "matrices are data): loss_functions.reproject_warp takes the stock-op path for an image or a "
+                           "matrix that requires grad")
+    gd = torch.ops.cerberus.reproject_warp_backward(image, depth, inv_K, proj, grad, ctx.eps) if ctx.needs_input_grad[1] else None
+    return None, gd, None, None, None
+
+
 def _no_double_backward(name):
     def _raise(ctx, *grads):
         raise RuntimeError("cerberus::%s is not differentiable (no double backward)" % name)
@@ -1073,6 +1152,9 @@ def _no_double_backward(name):
 torch.library.register_autograd("cerberus::photometric_loss", _photometric_backward, setup_context=_photometric_setup)
 torch.library.register_autograd("cerberus::edge_smoothness", _smoothness_backward, setup_context=_smoothness_setup)
 torch.library.register_autograd("cerberus::census_loss", _census_backward, setup_context=_census_setup)
+torch.library.register_autograd("cerberus::reproject_warp", _reproject_backward, setup_context=_reproject_setup)
+torch.library.register_autograd("cerberus::reproject_warp_backward", _no_double_backward("reproject_warp_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::census_loss_backward", _no_double_backward("census_loss_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::photometric_loss_backward", _no_double_backward("photometric_loss_backward"),

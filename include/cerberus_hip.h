@@ -352,6 +352,31 @@ int cerberus_corresponding_map(const void *data, void *map, void *workspace, int
 int cerberus_occlusion_mask_bidirection(const void *flow12, const void *flow21, void *mask, int B, int H,
                                         int W, float scale, float bias, int dtype, void *stream);
 
+/* The stereo reprojection warp of the depth reconstruction loss (additions only: no ABI bump): BackprojectDepth, Project3D
+ * and F.grid_sample(l_img, pix_coords, padding_mode="border") of DepthReconstructionLossV1 (depth_losses.py:112-206) as one
+ * launch each way, fp32.
+ *   image : (B,C,H,W), any C >= 1; a target image: it gets no gradient
+ *   depth : (B,1,H,W)
+ *   inv_K : (B,3,3) row-major, the upper-left 3 x 3 of the inverse intrinsics;  proj : (B,3,4) row-major, (K @ T)[:, :3, :].
+ *           Both in DEVICE memory, read by the kernels (no host copy, no synchronisation: capturable).
+ *   out   : (B,C,H,W), overwritten.  Pixel (x, y) samples the image at the position
+ *             u = inv_K . (x, y, 1);  p = proj . (depth * u, 1);  px = p.x / (p.z + eps),  py = p.y / (p.z + eps)
+ *           normalised as (px / (W - 1) - 0.5) * 2 and sampled with align_corners=False, border padding, bilinear: the sampling
+ *           rule of cerberus_flow_warp_forward(.., CERB_PAD_BORDER, CERB_INTERP_BILINEAR) at the flow (px - x, py - y).
+ *           Each step is rounded on its own, in the reference's order.  Positions are never written.
+ *   grad_depth : (B,1,H,W), every element written exactly once = sum_c grad_out[c] * d out[c] / d depth; a gather that
+ *           recomputes the positions: no atomics, no workspace, the same bits from run to run.  0 where the border clip holds
+ *           the position (ATen's rule).
+ * A NaN position gives NaN at that pixel only (the warp's rule); +-Inf positions are clipped to the border.  Nothing outside
+ * the tensors is read or written whatever the depth holds.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B or C <= 0, H or W < 2, B*C*H*W >= 2^31, a null
+ * pointer CERB_EINVAL -- all before any launch. */
+int cerberus_reproject_warp_forward(const void *image, const void *depth, const void *inv_K, const void *proj,
+                                    void *out, int B, int C, int H, int W, float eps, int dtype, void *stream);
+int cerberus_reproject_warp_backward(const void *image, const void *depth, const void *inv_K, const void *proj,
+                                     const void *grad_out, void *grad_depth, int B, int C, int H, int W, float eps,
+                                     int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
