@@ -12,8 +12,10 @@
 //   r = (in - 1) / (out - 1) (float, 0 when out == 1);  src = r * dst;  i0 = (int)src;
 //   i1 = i0 + (i0 < in - 1);  l1 = src - i0;  l0 = 1 - l1;
 //   out = l0y * (l0x * v00 + l1x * v01) + l1y * (l0x * v10 + l1x * v11)
-// The factor (2 or 4) multiplies the result: scaling by a power of two commutes exactly with
-// every rounding above, so factor * interp(flow) == interp(factor * flow) bit for bit.
+// The factor (any integer >= 1; the model uses 2 and 4) multiplies the result.  For a power of two the
+// scaling commutes exactly with every rounding above, so factor * interp(flow) == interp(factor * flow)
+// bit for bit; for the other factors the two differ by the rounding of one multiply
+// (tests/test_resample_gpu.py: factors 1 - 8 against float64 on every route of the backward).
 #include "common.h"
 
 namespace cerb {
@@ -36,6 +38,18 @@ __host__ __device__ inline float ratio(int in, int out) {
     return out > 1 ? static_cast<float>(in - 1) / static_cast<float>(out - 1) : 0.0f;
 }
 
+// factor * v, rounded to fp32 BEFORE the store converts it, whatever the storage type.  Without the barrier the compiler folds
+// the multiply and the fp16 conversion into one v_fma_mixlo_f16, which rounds the exact product once: for a factor that is no
+// power of two (the product is then inexact in fp32) the fp16 kernels differed from the fp32 and bf16 ones in the last bit
+// of an element in ~10^4 (tests/test_resample_gpu.py, factors 6 and 7).  One arithmetic for the three types: the 16-bit
+// kernels are the fp32 kernels with another ld / st.
+template <typename T>
+__device__ __forceinline__ float scaled(float v, float factor) {
+    float r = v * factor;
+    if constexpr (std::is_same<T, __half>::value) asm("" : "+v"(r));
+    return r;
+}
+
 // One workgroup per output row (grid-stride over planes x rows): the row's vertical tap is wave-uniform, the index
 // arithmetic 32-bit (round 2 decomposed a 64-bit flat index per element: 22.6 us for the 16.8 MB of the x 4 upsample).
 template <typename T>
@@ -55,7 +69,7 @@ __global__ __launch_bounds__(256) void upsample_fwd_kernel(const T *__restrict__
             const float v00 = ld(p0 + tx.i0), v01 = ld(p0 + tx.i1);
             const float v10 = ld(p1 + tx.i0), v11 = ld(p1 + tx.i1);
             const float v = ty.l0 * (tx.l0 * v00 + tx.l1 * v01) + ty.l1 * (tx.l0 * v10 + tx.l1 * v11);
-            st(o + ox, v * factor);
+            st(o + ox, scaled<T>(v, factor));
         }
     }
 }
@@ -77,8 +91,9 @@ __device__ __forceinline__ int last_dst(int i, float r, int out) {
 // matching columns are loaded, index arithmetic is 32-bit.  Same products, same order of additions: identical bits.
 // (In the host model's training step this kernel ran 14.8 times at 18.8 us on average -- the largest item of this
 // package's kernel time once the loss side was fixed: profiles/r05_kernel_stats_step_model.csv.)
-constexpr int kUpMaxCand = 16;   // candidate outputs per axis kept in registers: 2 * factor + 4 <= 16 up to factor 6
-constexpr int kUpMaxRows = 10;   // matching output rows staged in LDS (2 * factor + 1 <= 9 at factor 4)
+constexpr int kUpMaxCand = 16;   // candidate outputs per axis kept in registers: enough up to factor 5; wider windows (some columns at 6) loop
+constexpr int kUpMaxRows = 10;   // matching output rows staged in LDS (9, with a zero-weight tap 10, at factor 4 from H = 4 on;
+                                 // more rows -- factor >= 5, or H = 3 at factor 4 -- take the direct gather)
 constexpr int kUpMaxW = 1024;    // widest output row the LDS copy takes (40 KB for the ten rows)
 
 template <typename T>
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T *__restrict__
                         acc += s_wy[r] * row;
                     }
                 }
-                st(gin + rowi * W + x, acc * factor);
+                st(gin + rowi * W + x, scaled<T>(acc, factor));
             }
             __syncthreads();              // the next input row overwrites s_row / s_g
             continue;
@@ -213,7 +228,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const T *__restrict__
                     acc += wy * row;
                 }
             }
-            st(gin + rowi * W + x, acc * factor);
+            st(gin + rowi * W + x, scaled<T>(acc, factor));
         }
     }
 }

@@ -447,7 +447,9 @@ def _warp_correlation_leaky_cuda(input1, input2, flow, pad_mode, negative_slope)
 
 
 # ----------------------------------------------------------------------------
-# flow upsample (pwcnet_sfd.py:176, :199-201)
+# flow upsample (pwcnet_sfd.py:176, :199-201): factor 2 and 4 in the model, any integer factor >= 1 here
+# (tests/test_resample_gpu.py runs 1 - 8; exactly F.interpolate(flow * k) for powers of two, within one
+# rounding of a multiply otherwise)
 # ----------------------------------------------------------------------------
 def _flow_upsample_run(t, factor, forward, what):
     if t.dim() != 4:
