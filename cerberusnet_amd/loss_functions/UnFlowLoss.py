@@ -87,7 +87,10 @@ def _ssim_distance(x, y):
     """(1 - SSIM) / 2 on 3x3 windows with reflection padding, clamped to [0, 1]
     (``loss_functions.py:47-77``)."""
     import torch.nn.functional as F
-    pool = lambda t: F.avg_pool2d(F.pad(t, (1, 1, 1, 1), mode="reflect"), 3, 1)
+    # the reference's op sequence: both images padded once, products of the padded images pooled (the same forward bits as
+    # pooling padded products, and the reference's summation order in the backward as well)
+    x, y = F.pad(x, (1, 1, 1, 1), mode="reflect"), F.pad(y, (1, 1, 1, 1), mode="reflect")
+    pool = lambda t: F.avg_pool2d(t, 3, 1)
     c1, c2 = 0.01 ** 2, 0.03 ** 2
     mu_x, mu_y = pool(x), pool(y)
     var_x = pool(x ** 2) - mu_x ** 2

@@ -4,7 +4,10 @@ Yardstick for values and gradients: the package's own stock-op formulation (``un
 ``loss_photometric`` / ``_edge_aware_smoothness``) evaluated in float64 on the CPU.  Values: relative error <= 1e-5 (the
 figure of the hip-vs-torch loss agreement in test_loss_side_gpu).  Gradients: ``l2_err`` and ``rel_err`` against float64,
 each at most 4 x the same error of the stock fp32 chain run on the GPU in the same test (the factor allows for another,
-equally valid operation order and nothing more)."""
+equally valid operation order and nothing more).
+
+The tests at the end of the file hold the same ops, and unFlowLoss away from its default keywords, to results of the
+reference's own code (tests/golden/photometric.npz)."""
 import functools
 
 import numpy as np
@@ -12,6 +15,7 @@ import pytest
 import torch
 
 import cerberusnet_amd as ca
+import photometric_cases as pc
 from cerberusnet_amd.loss_functions import UnFlowLoss as U
 from cerberusnet_amd.loss_functions.UnFlowLoss import unFlowLoss
 from cerberusnet_amd.synth import hash_uniform
@@ -312,3 +316,106 @@ def test_photometric_loss_graphed_replay_is_bit_equal_to_eager():
         g, = torch.autograd.grad(v, r)
         assert torch.equal(g_v, v.detach()), (i, float(g_v), float(v))
         assert torch.equal(g_g, g), i
+
+
+# ---- held to the reference itself: tests/golden/photometric.npz holds what the reference's own SSIM module,
+# smooth_grad_1st / smooth_grad_2nd and unFlowLoss compute on the CPU in float32 and in float64 for the cases of
+# tests/photometric_cases.py.  Values: within VALUE_TOL of the reference's float64 value.  Gradients: l2_err and rel_err
+# against the reference's float64 gradient, each at most GRAD_FACTOR x the same error of the reference's float32 gradient
+# (formed on the CPU; the tests above take the stock chain on the GPU, whose error is printed beside it: no case needs it
+# as a second yardstick). ----------------------------------------------------------------------------------------------
+
+
+@pytest.fixture(scope="module")
+def ref(golden):
+    return golden("photometric")
+
+
+def _bracket(name, fused, stock_gpu, ref32, ref64):
+    for metric in (l2_err, rel_err):
+        ef, ec, eg = metric(fused, ref64), metric(ref32, ref64), metric(stock_gpu, ref64)
+        print("%s %s: fused %.3e reference float32 %.3e (ratio %.2f) stock fp32 on the GPU %.3e" % (
+            name, metric.__name__, ef, ec, ef / ec if ec else float(ef > 0), eg))
+        assert ef <= GRAD_FACTOR * ec, (name, metric.__name__, ef, ec, eg)
+
+
+@pytest.mark.parametrize("weights", pc.WEIGHT_PAIRS)
+@pytest.mark.parametrize("i", range(len(pc.PHOTO_CASES)))
+def test_photometric_loss_against_the_reference_golden(ref, i, weights):
+    shape, family = pc.PHOTO_CASES[i]
+    orig, recons = pc.photo_images(i)
+    want_v, want64 = pc.photo_reference(ref, i, "f64", *weights)
+    _, want32 = pc.photo_reference(ref, i, "f32", *weights)
+    for k, which in enumerate(("im_orig", "im_recons")):          # one call per image that asks for a gradient
+        pair = [dev(orig), dev(recons)]
+        pair[k].requires_grad_(True)
+        v = ca.photometric_loss(pair[0], pair[1], *weights)
+        g, = torch.autograd.grad(v, pair[k])
+        spair = [dev(orig), dev(recons)]
+        spair[k].requires_grad_(True)
+        vs = U._photometric_stock(spair[0], spair[1], *weights)
+        gs, = torch.autograd.grad(vs, spair[k])
+        name = "reference photometric %d %s %s %s d/d %s" % (i, shape, family, weights, which)
+        print("%s value: fused rel %.3e stock fp32 on the GPU rel %.3e" % (name, abs(v.item() - want_v) / abs(want_v),
+                                                                          abs(vs.item() - want_v) / abs(want_v)))
+        assert v.shape == () and v.dtype == torch.float32
+        assert abs(v.item() - want_v) <= VALUE_TOL * abs(want_v)
+        _bracket(name, g.cpu().numpy(), gs.cpu().numpy(), want32[k], want64[k])
+
+
+@pytest.mark.parametrize("i", range(len(pc.SMOOTH_CASES)))
+def test_edge_smoothness_against_the_reference_golden(ref, i):
+    shape, channels, degree, alpha, family = pc.SMOOTH_CASES[i]
+    flow, image = pc.smooth_inputs(i)
+    want_v = float(ref["s%d_f64_value" % i])
+    f = dev(flow).requires_grad_(True)
+    v = ca.edge_smoothness(f, dev(image), alpha, degree)
+    g, = torch.autograd.grad(v, f)
+    fs = dev(flow).requires_grad_(True)
+    vs = U._edge_aware_smoothness(fs, dev(image), alpha, degree)
+    gs, = torch.autograd.grad(vs, fs)
+    name = "reference smoothness %d %s degree %d alpha %g %s" % (i, shape, degree, alpha, family)
+    print("%s value: fused rel %.3e stock fp32 on the GPU rel %.3e" % (name, abs(v.item() - want_v) / abs(want_v),
+                                                                      abs(vs.item() - want_v) / abs(want_v)))
+    assert v.shape == () and v.dtype == torch.float32
+    assert abs(v.item() - want_v) <= VALUE_TOL * abs(want_v)
+    _bracket(name, g.cpu().numpy(), gs.cpu().numpy(), ref["s%d_f32_grad_flow" % i], ref["s%d_f64_grad_flow" % i])
+    # an image that asks for a gradient takes the stock path by design: held to the reference's gradients all the same
+    f2, im2 = dev(flow).requires_grad_(True), dev(image).requires_grad_(True)
+    v2 = ca.edge_smoothness(f2, im2, alpha, degree)
+    gf2, gi2 = torch.autograd.grad(v2, (f2, im2))
+    ei, ef = rel_err(gi2.cpu().numpy(), ref["s%d_f64_grad_image" % i]), rel_err(gf2.cpu().numpy(), ref["s%d_f64_grad_flow" % i])
+    print("%s with an image gradient: value rel %.3e image gradient rel_err %.3e flow gradient rel_err %.3e" % (
+        name, abs(v2.item() - want_v) / abs(want_v), ei, ef))
+    assert abs(v2.item() - want_v) <= VALUE_TOL * abs(want_v)
+    assert ei < 1e-5 and ef < 1e-5
+
+
+@pytest.mark.parametrize("name,fused", [("a", True), ("a", False), ("b", True), ("b", False), ("c", True)])
+def test_unflow_loss_keywords_against_the_reference_golden(ref, monkeypatch, name, fused):
+    """unFlowLoss(backend='hip') away from the default keywords (tests/photometric_cases.py: consistency, weight, smooth,
+    w_sm_scales, w_wrp_scales) against the reference's own float64 run; bounds of
+    test_unflow_loss_with_occlusion_matches_float64: value 1e-5 relative, flow gradients l2_err < 5e-3.  (c) carries a
+    ternary weight, which needs fused=True.  With fused=True no stock formulation runs."""
+    l_img, l_seq, fw, bw = pc.loss_inputs()
+    fw = [f.detach().to(DEV).requires_grad_(True) for f in fw]
+    bw = [f.detach().to(DEV).requires_grad_(True) for f in bw]
+    if fused:
+        def boom(*_a, **_k):
+            raise AssertionError("a stock formulation was taken with fused=True")
+        for fn in ("_ssim_distance", "_edge_aware_smoothness", "TernaryLoss", "_photometric_stock"):
+            monkeypatch.setattr(U, fn, boom)
+    loss = unFlowLoss(fused=fused, **pc.LOSS_CONFIGS[name])({"flow": fw, "flow_b": bw}, {"l_img": l_img.to(DEV), "l_seq": l_seq.to(DEV)})
+    grads = torch.autograd.grad(loss, fw + bw, allow_unused=True)
+    want = float(ref["l%s_f64_value" % name])
+    print("reference unFlowLoss %s fused=%s: GPU %.9g reference float64 %.12g (rel %.3e)" % (
+        name, fused, float(loss.detach()), want, abs(float(loss.detach()) - want) / abs(want)))
+    assert abs(float(loss.detach()) - want) <= 1e-5 * abs(want)
+    used = pc.loss_used(name)
+    for j, g in enumerate(grads):
+        if j not in used:
+            assert g is None, (name, j)
+            continue
+        err = l2_err(g.cpu().numpy(), ref["l%s_grad%d" % (name, j)])
+        print("  flow %d gradient l2_err vs the reference's float64: %.3e" % (j, err))
+        assert err < 5e-3
