@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
-// census.hip, occlusion.hip and reproject.hip.
+// census.hip, occlusion.hip, reproject.hip and seg_loss.hip.
 #include <atomic>
 #include <cstring>
 
@@ -436,6 +436,54 @@ int cerberus_reproject_warp_backward(const void *image, const void *depth, const
     if (!image || !depth || !inv_K || !proj || !grad_out || !grad_depth) return CERB_EINVAL;
     return reproject_warp_backward(image, depth, inv_K, proj, grad_out, grad_depth, B, C, H, W, eps,
                                    static_cast<hipStream_t>(stream));
+}
+
+// the segmentation loss: logits (B,C,H,W) fp32, labels (B,H,W) int64.  Pixels are counted with an int (a workgroup's last
+// pixel index may run 1023 past the end before it is tested); offsets into the logits are 64-bit.
+static int seg_ce_args_ok(int B, int C, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B < 0 || C < 2 || H <= 0 || W <= 0) return CERB_EINVAL;
+    if (static_cast<int64_t>(B) * H * W > 0x7fffffff - 1024) return CERB_ETOOLARGE;
+    return CERB_OK;
+}
+
+int64_t cerberus_seg_cross_entropy_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || static_cast<int64_t>(B) * H * W > 0x7fffffff - 1024) return 0;
+    return seg_ce_workspace_bytes(B, H, W);
+}
+
+int cerberus_seg_cross_entropy_forward(const void *logits, const void *target, const void *weight, void *loss, void *lse,
+                                       void *state, void *workspace, int64_t workspace_bytes, int B, int C, int H, int W,
+                                       int64_t ignore_index, float gamma, int dtype, void *stream) {
+    const int rc = seg_ce_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (!(gamma >= 0.f)) return CERB_EINVAL;                     // a NaN gamma too
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !weight || !loss || !lse || !state || !workspace) return CERB_EINVAL;
+    if (workspace_bytes < seg_ce_workspace_bytes(B, H, W)) return CERB_EINVAL;
+    return seg_ce_forward(logits, target, weight, loss, lse, state, workspace, B, C, H, W, ignore_index, gamma,
+                          static_cast<hipStream_t>(stream));
+}
+
+int cerberus_seg_cross_entropy_backward(const void *logits, const void *target, const void *weight, const void *lse,
+                                        const void *state, const void *grad_loss, void *grad_logits, int B, int C, int H, int W,
+                                        int64_t ignore_index, int dtype, void *stream) {
+    const int rc = seg_ce_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !weight || !lse || !state || !grad_loss || !grad_logits) return CERB_EINVAL;
+    return seg_ce_backward(logits, target, weight, lse, state, grad_loss, grad_logits, B, C, H, W, ignore_index,
+                           static_cast<hipStream_t>(stream));
+}
+
+int cerberus_class_histogram(const void *target, void *counts, int64_t count, int num_classes, int64_t ignore_index, void *stream) {
+    if (count < 0 || num_classes < 1) return CERB_EINVAL;
+    if (num_classes > class_histogram_max_classes()) return CERB_EUNSUPPORTED;
+    if (count > (static_cast<int64_t>(1) << 40)) return CERB_ETOOLARGE;       // a workgroup's 32-bit LDS bins cannot wrap
+    if (count == 0) return CERB_OK;
+    if (!target || !counts) return CERB_EINVAL;
+    return class_histogram(target, counts, count, num_classes, ignore_index, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

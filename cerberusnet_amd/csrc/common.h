@@ -244,6 +244,17 @@ int reproject_warp_forward(const void *image, const void *depth, const void *inv
 int reproject_warp_backward(const void *image, const void *depth, const void *inv_k, const void *proj, const void *grad_out,
                             void *grad_depth, int B, int C, int H, int W, float eps, hipStream_t s);
 
+// seg_loss.hip: the segmentation head's weighted cross-entropy with the focal factor of its mean as a scalar op (fp32 logits
+// (B,C,H,W), int64 labels (B,H,W), fp32 class weights (C,)), and the class histogram of a label map; arguments are checked by
+// api.hip.  `loss` / `grad_loss` point to ONE float in device memory, `state` to four.
+int64_t seg_ce_workspace_bytes(int B, int H, int W);
+int seg_ce_forward(const void *logits, const void *target, const void *weight, void *loss, void *lse, void *state, void *workspace,
+                   int B, int C, int H, int W, int64_t ignore_index, float gamma, hipStream_t s);
+int seg_ce_backward(const void *logits, const void *target, const void *weight, const void *lse, const void *state,
+                    const void *grad_loss, void *grad_logits, int B, int C, int H, int W, int64_t ignore_index, hipStream_t s);
+int class_histogram_max_classes();
+int class_histogram(const void *target, void *counts, int64_t count, int num_classes, int64_t ignore_index, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

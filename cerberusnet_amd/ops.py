@@ -68,6 +68,11 @@ _def.define("corresponding_map(Tensor data, bool is_flow) -> Tensor")
 _def.define("occlusion_mask_bidirection(Tensor flow12, Tensor flow21, float scale, float bias) -> Tensor")
 _def.define("reproject_warp(Tensor image, Tensor depth, Tensor inv_K, Tensor proj, float eps) -> Tensor")
 _def.define("reproject_warp_backward(Tensor image, Tensor depth, Tensor inv_K, Tensor proj, Tensor grad_out, float eps) -> Tensor")
+_def.define("seg_cross_entropy(Tensor logits, Tensor target, Tensor weight, int ignore_index, float gamma) -> "
+            "(Tensor loss, Tensor lse, Tensor state)")
+_def.define("seg_cross_entropy_backward(Tensor logits, Tensor target, Tensor weight, Tensor lse, Tensor state, Tensor grad_loss, "
+            "int ignore_index) -> Tensor")
+_def.define("class_histogram(Tensor target, int num_classes, int ignore_index) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -865,6 +870,103 @@ def _reproject_warp_backward_cuda(image, depth, inv_K, proj, grad_out, eps):
     return grad
 
 
+# the segmentation loss (seg_losses.py:121-190), csrc/seg_loss.hip
+SEG_CHUNK_PIXELS = 1024                 # pixels per workgroup of the forward: one num and one den partial each
+HISTOGRAM_MAX_CLASSES = 2048            # the LDS bins of class_histogram; more classes: torch.bincount in the wrapper
+
+
+def _seg_workspace_bytes(B, H, W):
+    """cerberus_seg_cross_entropy_workspace_bytes in pure Python (a test holds the two equal): an fp32 num and an fp32 den
+    partial per 1024 pixels of the flattened (B,H,W) map."""
+    if B <= 0 or H <= 0 or W <= 0 or B * H * W > 0x7fffffff - 1024:
+        return 0
+    return 2 * ((B * H * W + SEG_CHUNK_PIXELS - 1) // SEG_CHUNK_PIXELS) * 4
+
+
+def _seg_check(logits, target, weight, what):
+    if logits.dim() != 4:
+        raise RuntimeError("%s: logits must be a 4-D (B,C,H,W) tensor, got %s" % (what, tuple(logits.shape)))
+    if logits.dtype != torch.float32:
+        raise RuntimeError("%s: logits must be float32, got %s (16-bit logits take the stock-op path of "
+                           "loss_functions.seg_cross_entropy)" % (what, logits.dtype))
+    if target.dtype != torch.int64:
+        raise RuntimeError("%s: target must be int64, got %s" % (what, target.dtype))
+    if weight.dtype != torch.float32:
+        raise RuntimeError("%s: weight must be float32, got %s" % (what, weight.dtype))
+    if target.device != logits.device or weight.device != logits.device:
+        raise RuntimeError("%s: inputs on different devices: %s, %s, %s" % (what, logits.device, target.device, weight.device))
+    B, C, H, W = logits.shape
+    if tuple(target.shape) != (B, H, W):
+        raise RuntimeError("%s: target must be (B,H,W) = %s, got %s" % (what, (B, H, W), tuple(target.shape)))
+    if tuple(weight.shape) != (C,):
+        raise RuntimeError("%s: weight must hold one value per class, (%d,), got %s" % (what, C, tuple(weight.shape)))
+    if C < 2 or logits.numel() == 0:
+        raise RuntimeError("%s: needs at least 2 classes and one pixel, got %s (loss_functions.seg_cross_entropy takes the "
+                           "stock-op path)" % (what, tuple(logits.shape)))
+
+
+def _seg_cross_entropy_cuda(logits, target, weight, ignore_index, gamma):
+    what = "cerberus::seg_cross_entropy"
+    _seg_check(logits, target, weight, what)
+    x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    B, C, H, W = x.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_seg_cross_entropy_workspace_bytes(B, H, W)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    lse = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+    state = torch.empty((4,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.cerberus_seg_cross_entropy_forward(x.data_ptr(), t.data_ptr(), w.data_ptr(), loss.data_ptr(), lse.data_ptr(),
+                                                    state.data_ptr(), ws.data_ptr(), ws_bytes, B, C, H, W, int(ignore_index),
+                                                    ctypes.c_float(gamma), 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return loss, lse, state
+
+
+def _seg_cross_entropy_meta(logits, target, weight, ignore_index, gamma):
+    B, _, H, W = logits.shape
+    f = lambda *shape: logits.new_empty(shape, dtype=torch.float32)
+    return f(), f(B, H, W), f(4)
+
+
+def _seg_cross_entropy_backward_cuda(logits, target, weight, lse, state, grad_loss, ignore_index):
+    what = "cerberus::seg_cross_entropy_backward"
+    _seg_check(logits, target, weight, what)
+    B, C, H, W = logits.shape
+    for t, name, shape in ((lse, "lse", (B, H, W)), (state, "state", (4,))):
+        if t.dtype != torch.float32 or t.device != logits.device or tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s must be the float32 %s tensor of the forward, got %s %s" % (what, name, shape, t.dtype,
+                                                                                                  tuple(t.shape)))
+    x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    g = _grad_scalar(grad_loss, x, what)
+    grad = torch.empty_like(x)          # every element is written by the kernel
+    with torch.cuda.device(x.device):
+        rc = _lib.get().cerberus_seg_cross_entropy_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), lse.contiguous().data_ptr(),
+                                                            state.contiguous().data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H,
+                                                            W, int(ignore_index), 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return grad
+
+
+def _class_histogram_cuda(target, num_classes, ignore_index):
+    what = "cerberus::class_histogram"
+    if target.dtype != torch.int64:
+        raise RuntimeError("%s: target must be int64, got %s" % (what, target.dtype))
+    if not 1 <= num_classes <= HISTOGRAM_MAX_CLASSES:
+        raise RuntimeError("%s: num_classes must lie in 1..%d, got %d (loss_functions.class_balance_weights takes "
+                           "torch.bincount above it)" % (what, HISTOGRAM_MAX_CLASSES, num_classes))
+    t = target.contiguous()
+    if t.numel() == 0:
+        return torch.zeros((num_classes,), dtype=torch.int64, device=t.device)
+    counts = torch.empty((num_classes,), dtype=torch.int64, device=t.device)      # zeroed on the stream by the call
+    with torch.cuda.device(t.device):
+        rc = _lib.get().cerberus_class_histogram(t.data_ptr(), counts.data_ptr(), t.numel(), int(num_classes), int(ignore_index),
+                                                 _stream_ptr(t))
+    _lib.check(rc, what)
+    return counts
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -908,6 +1010,15 @@ _def.impl("reproject_warp", _no_cpu("reproject_warp"), "CPU")
 _def.impl("reproject_warp_backward", _reproject_warp_backward_cuda, "CUDA")
 _def.impl("reproject_warp_backward", lambda image, depth, k, p, g, eps: depth.new_empty(depth.shape), "Meta")
 _def.impl("reproject_warp_backward", _no_cpu("reproject_warp_backward"), "CPU")
+_def.impl("seg_cross_entropy", _seg_cross_entropy_cuda, "CUDA")
+_def.impl("seg_cross_entropy", _seg_cross_entropy_meta, "Meta")
+_def.impl("seg_cross_entropy", _no_cpu("seg_cross_entropy"), "CPU")
+_def.impl("seg_cross_entropy_backward", _seg_cross_entropy_backward_cuda, "CUDA")
+_def.impl("seg_cross_entropy_backward", lambda x, t, w, lse, st, g, i: torch.empty_like(x), "Meta")
+_def.impl("seg_cross_entropy_backward", _no_cpu("seg_cross_entropy_backward"), "CPU")
+_def.impl("class_histogram", _class_histogram_cuda, "CUDA")
+_def.impl("class_histogram", lambda t, c, i: t.new_empty((c,), dtype=torch.int64), "Meta")
+_def.impl("class_histogram", _no_cpu("class_histogram"), "CPU")
 _def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
 _def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
 _def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
@@ -1145,6 +1256,30 @@ def _reproject_backward(ctx, grad):
     return None, gd, None, None, None
 
 
+def _seg_setup(ctx, inputs, output):
+    logits, target, weight, ignore_index, _gamma = inputs
+    loss, lse, state = output
+    # the logits, and what the forward left for the backward: lse (4 B per pixel against 4 C) and the scalars on the device
+    ctx.save_for_backward(logits, target, weight, lse, state)
+    ctx.ignore_index = ignore_index
+    ctx.mark_non_differentiable(lse, state)
+
+
+def _seg_backward(ctx, grad_loss, _grad_lse, _grad_state):
+    logits, target, weight, lse, state = ctx.saved_tensors
+    if ctx.needs_input_grad[2]:
+        raise RuntimeError("cerberus::seg_cross_entropy has no gradient for its class weights: "
+                           "loss_functions.seg_cross_entropy takes the stock-op path for a weight that requires grad")
+    gx = None
+    if ctx.needs_input_grad[0]:
+        gx = torch.ops.cerberus.seg_cross_entropy_backward(logits, target, weight, lse, state, grad_loss, ctx.ignore_index)
+    return gx, None, None, None, None
+
+
+def _histogram_backward(ctx, grad):
+    raise RuntimeError("cerberus::class_histogram is not differentiable: it counts integer labels")
+
+
 def _no_double_backward(name):
     def _raise(ctx, *grads):
         raise RuntimeError("cerberus::%s is not differentiable (no double backward)" % name)
@@ -1163,3 +1298,7 @@ torch.library.register_autograd("cerberus::photometric_loss_backward", _no_doubl
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::edge_smoothness_backward", _no_double_backward("edge_smoothness_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::seg_cross_entropy", _seg_backward, setup_context=_seg_setup)
+torch.library.register_autograd("cerberus::seg_cross_entropy_backward", _no_double_backward("seg_cross_entropy_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::class_histogram", _histogram_backward, setup_context=lambda ctx, inputs, output: None)

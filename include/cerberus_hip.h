@@ -377,6 +377,50 @@ int cerberus_reproject_warp_backward(const void *image, const void *depth, const
                                      const void *grad_out, void *grad_depth, int B, int C, int H, int W, float eps,
                                      int dtype, void *stream);
 
+/* The segmentation head's loss as one differentiable scalar (additions only: no ABI bump): FocalLoss2D / SegCrossEntropy
+ * (seg_losses.py:121-190), that is F.cross_entropy(logits, target, weight=w, ignore_index=i) reduced to a mean, times the
+ * focal factor of that MEAN (the reference applies it to the scalar, :150-154).
+ *   logits : (B,C,H,W) fp32, C >= 2, any C (the kernels stream over the classes);  target : (B,H,W) int64;
+ *   weight : (C,) fp32, in DEVICE memory;  ignore_index : any integer;  gamma >= 0
+ *   valid(p) = target(p) != ignore_index;  lse(p) = log sum_c exp(x_c(p)) (max-subtracted, expf / logf)
+ *   num = sum_{valid p} w[t(p)] (lse(p) - x_t(p));  den = sum_{valid p} w[t(p)];  ce = num / den
+ *   loss[0] = ce for gamma == 0 (exactly), else (1 - exp(-ce))^gamma * ce
+ *   lse    : (B,H,W) fp32, overwritten (every pixel, ignored ones too): the backward reads it instead of a second pass
+ *   state  : 4 floats, overwritten: [ce, den, (dloss/dce) / den, 0], read by the backward on the device
+ *   workspace : cerberus_seg_cross_entropy_workspace_bytes(B,H,W) bytes (a num and a den partial per 1024 pixels; 0 for a
+ *            non-positive or too large size), fully overwritten; no zero-fill needed
+ * Forward: one pass over the logits (a lane owns 4 consecutive pixels and loads 16 bytes per class plane when H*W % 4 == 0
+ * and logits, target and lse are 16-byte aligned; one pixel per lane otherwise -- both routes give the same bits) and a
+ * single-workgroup fixed-order sum: no floating-point atomics, bit-reproducible for a given shape.
+ * Backward: grad_logits (B,C,H,W) = grad_loss[0] * state[2] * w[t] * (softmax - onehot), every element written exactly once
+ * (no zero-fill); exactly 0.0f at ignored pixels, at out-of-range labels and at pixels of weight 0 (a select: also when
+ * state[2] is NaN).  grad_loss points to ONE float in DEVICE memory (no host synchronisation: capturable).
+ * Every valid pixel ignored, or den == 0: loss NaN (0 / 0, as stock), gradient all zeros.  A NaN logit at a valid pixel
+ * gives a NaN loss; at an ignored pixel it changes nothing.  A label outside [0, C) that is not ignore_index never forms
+ * an address: it adds NaN to num (stock PyTorch raises a device-side assertion) and its gradient is zeros.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, C < 2, H or W <= 0, gamma < 0 or NaN
+ * CERB_EINVAL; B*H*W > 2^31 - 1025 CERB_ETOOLARGE; then B == 0 returns 0 without a launch; a null pointer, a workspace that
+ * is too small CERB_EINVAL -- all before any launch.
+ *
+ * cerberus_class_histogram: counts[c] = the number of labels equal to c, for c in [0, num_classes) other than ignore_index
+ * (the counts of the reference's dynamic class weights, :144-147, without unique()).
+ *   target : `count` int64 labels;  counts : num_classes int64, zeroed on the stream by the call itself (a kernel: capturable) and
+ *   added to with integer adds (LDS per workgroup, then global): any order, the same result.  Labels outside
+ *   [0, num_classes) are not counted.
+ * Errors: count < 0, num_classes < 1 CERB_EINVAL; num_classes > 2048 CERB_EUNSUPPORTED; count > 2^40 CERB_ETOOLARGE; then
+ * count == 0 returns 0 and touches nothing; a null pointer CERB_EINVAL. */
+int64_t cerberus_seg_cross_entropy_workspace_bytes(int B, int H, int W);
+int cerberus_seg_cross_entropy_forward(const void *logits, const void *target, const void *weight, void *loss,
+                                       void *lse, void *state, void *workspace, int64_t workspace_bytes, int B,
+                                       int C, int H, int W, int64_t ignore_index, float gamma, int dtype,
+                                       void *stream);
+int cerberus_seg_cross_entropy_backward(const void *logits, const void *target, const void *weight,
+                                        const void *lse, const void *state, const void *grad_loss,
+                                        void *grad_logits, int B, int C, int H, int W, int64_t ignore_index,
+                                        int dtype, void *stream);
+int cerberus_class_histogram(const void *target, void *counts, int64_t count, int num_classes,
+                             int64_t ignore_index, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
