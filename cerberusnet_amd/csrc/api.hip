@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
-// census.hip, occlusion.hip, reproject.hip and seg_loss.hip.
+// census.hip, occlusion.hip, reproject.hip, seg_loss.hip and depth_loss.hip.
 #include <atomic>
 #include <cstring>
 
@@ -484,6 +484,42 @@ int cerberus_class_histogram(const void *target, void *counts, int64_t count, in
     if (count == 0) return CERB_OK;
     if (!target || !counts) return CERB_EINVAL;
     return class_histogram(target, counts, count, num_classes, ignore_index, static_cast<hipStream_t>(stream));
+}
+
+// the supervised depth loss: prediction (B,h,w), ground truth (B,H,W), fp32.  Pixels of the prediction are counted with an int
+// (a workgroup's last pixel index may run 1023 past the end before it is tested); offsets into the ground truth are 64-bit.
+static int inv_huber_args_ok(int B, int h, int w, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B < 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return CERB_EINVAL;
+    if (H % h != 0 || W % w != 0) return CERB_EUNSUPPORTED;     // the caller resizes the ground truth for any other ratio
+    if (static_cast<int64_t>(B) * h * w > 0x7fffffff - 1024) return CERB_ETOOLARGE;
+    return CERB_OK;
+}
+
+int64_t cerberus_inv_huber_workspace_bytes(int B, int h, int w) {
+    if (B <= 0 || h <= 0 || w <= 0 || static_cast<int64_t>(B) * h * w > 0x7fffffff - 1024) return 0;
+    return inv_huber_workspace_bytes(B, h, w);
+}
+
+int cerberus_inv_huber_forward(const void *pred, const void *gt, void *loss, void *state, void *workspace, int64_t workspace_bytes,
+                               int B, int h, int w, int H, int W, int dtype, void *stream) {
+    const int rc = inv_huber_args_ok(B, h, w, H, W, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!pred || !gt || !loss || !state || !workspace) return CERB_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return CERB_EINVAL;
+    if (workspace_bytes < inv_huber_workspace_bytes(B, h, w)) return CERB_EINVAL;
+    return inv_huber_forward(pred, gt, loss, state, workspace, B, h, w, H, W, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_inv_huber_backward(const void *pred, const void *gt, const void *state, const void *grad_loss, void *grad_pred, int B,
+                                int h, int w, int H, int W, int dtype, void *stream) {
+    const int rc = inv_huber_args_ok(B, h, w, H, W, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!pred || !gt || !state || !grad_loss || !grad_pred) return CERB_EINVAL;
+    return inv_huber_backward(pred, gt, state, grad_loss, grad_pred, B, h, w, H, W, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

@@ -255,6 +255,15 @@ int seg_ce_backward(const void *logits, const void *target, const void *weight, 
 int class_histogram_max_classes();
 int class_histogram(const void *target, void *counts, int64_t count, int num_classes, int64_t ignore_index, hipStream_t s);
 
+// depth_loss.hip: the supervised depth loss InvHuberLoss (berHu) as a scalar op, fp32: prediction (B,h,w), ground truth (B,H,W)
+// with H % h == 0 and W % w == 0 (a pyramid level gathers gt[b, y H/h, x W/w]); arguments are checked by api.hip.  `loss` /
+// `grad_loss` point to ONE float in device memory, `state` to four; `workspace` is 16-byte aligned.
+int64_t inv_huber_workspace_bytes(int B, int h, int w);
+int inv_huber_forward(const void *pred, const void *gt, void *loss, void *state, void *workspace, int B, int h, int w, int H, int W,
+                      hipStream_t s);
+int inv_huber_backward(const void *pred, const void *gt, const void *state, const void *grad_loss, void *grad_pred, int B, int h, int w,
+                       int H, int W, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

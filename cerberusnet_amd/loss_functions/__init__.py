@@ -1,4 +1,5 @@
-from .depth_losses import BackprojectDepth, DepthReconstructionLossV1, Project3D, reproject_warp
+from .depth_losses import (BackprojectDepth, DepthAwareLoss, DepthReconstructionLossV1, InvHuberLoss, InvHuberLossPyr, Project3D,
+                           ScaleInvariantError, inv_huber_loss, reproject_warp)
 from .seg_losses import FocalLoss2D, SegCrossEntropy, class_balance_weights, seg_cross_entropy
 from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, get_corresponding_map, get_occu_mask_backward,
                          get_occu_mask_bidirection, mesh_grid, norm_grid, photometric_loss, unFlowLoss)
@@ -6,4 +7,5 @@ from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, g
 __all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoothness", "TernaryLoss", "census_loss",
            "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "unFlowLoss",
            "BackprojectDepth", "Project3D", "DepthReconstructionLossV1", "reproject_warp",
-           "seg_cross_entropy", "class_balance_weights", "FocalLoss2D", "SegCrossEntropy"]
+           "seg_cross_entropy", "class_balance_weights", "FocalLoss2D", "SegCrossEntropy",
+           "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss"]

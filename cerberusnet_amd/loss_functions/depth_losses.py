@@ -8,13 +8,21 @@ launch (``cerberus::reproject_warp``, ``csrc/reproject.hip``) with a one-launch 
 
 The sampling rule is ``flow_warp``'s: positions are normalised by (W-1), (H-1) and sampled with ``align_corners=False``
 (quirk Q2), bilinear, border padding.
+
+The supervised losses of the same file (:16-110) keep their names, constructor signatures and ``forward(predictions,
+targets)`` with the keys ``'depth'`` and ``'disparity'``.  ``InvHuberLoss`` (the one a reference config trains with) and
+``InvHuberLossPyr`` have a fused HIP path (``cerberus::inv_huber``, ``csrc/depth_loss.hip``: two passes and a finish forward,
+one launch backward, the gradient through the data-dependent cutoff included); ``ScaleInvariantError`` and ``DepthAwareLoss``
+are restated in stock ops so that they can be differentiated at all (the reference's in-place ``+= 0.001`` makes its
+backward raise).
 """
 import torch
 import torch.nn.functional as F
 
 from .UnFlowLoss import _ssim_distance, photometric_loss
 
-__all__ = ["BackprojectDepth", "Project3D", "DepthReconstructionLossV1", "reproject_warp"]
+__all__ = ["BackprojectDepth", "Project3D", "DepthReconstructionLossV1", "reproject_warp",
+           "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss"]
 
 
 class BackprojectDepth(torch.nn.Module):
@@ -132,3 +140,180 @@ class DepthReconstructionLossV1(torch.nn.Module):
         else:
             loss = abs_diff.mean(1, True)
         return loss.mean()
+
+
+# ---- the supervised depth losses (reference :16-110) --------------------------------------------------------------------
+def _map3(t, name):
+    """A (B,1,h,w) map as (B,h,w); a (B,h,w) one as it is."""
+    if t.dim() == 4 and t.shape[1] == 1:
+        return t.squeeze(1)
+    if t.dim() == 3:
+        return t
+    raise ValueError(f"Invalid {name} shape {tuple(t.shape)}: (B,1,h,w) or (B,h,w)")
+
+
+def _nearest(gt, size):
+    return F.interpolate(gt.unsqueeze(1), tuple(size), mode="nearest").squeeze(1)
+
+
+def _inv_huber_stock(pred, gt):
+    """The reference's ``InvHuberLoss.forward`` (:78-87) without ``weight``, in its operation order; ``pred`` and ``gt`` (B,h,w)."""
+    pred_relu = F.relu(pred)
+    diff = pred_relu - gt
+    mask = gt > 0
+    err = (diff * mask.float()).abs()
+    c = 0.2 * err.max()
+    err2 = (diff**2 + c**2) / (2. * c)
+    mask_err = err <= c
+    mask_err2 = err > c
+    return (err * mask_err.float() + err2 * mask_err2.float()).mean()
+
+
+def _inv_huber_fusable(pred, gt):
+    """What cerberus::inv_huber takes: fp32 tensors on one GPU, at least a pixel, a ground truth that wants no gradient."""
+    if not (pred.is_cuda and gt.device == pred.device and pred.dtype == torch.float32 and gt.dtype == torch.float32):
+        return False
+    if pred.numel() == 0 or gt.numel() == 0 or pred.shape[0] != gt.shape[0]:
+        return False
+    return not (torch.is_grad_enabled() and gt.requires_grad)
+
+
+def inv_huber_loss(pred, gt):
+    """The inverse Huber (berHu) loss of ``InvHuberLoss`` (reference :64-88) as a 0-dim tensor.  ``pred`` (B,1,h,w) or
+    (B,h,w), ``gt`` (B,H,W) (or (B,1,H,W)); a ground truth of another size is compared as
+    ``F.interpolate(gt, (h, w), mode='nearest')``.  With ``d = relu(pred) - gt`` and ``err = |d|`` where ``gt > 0``, else 0::
+
+        c = 0.2 * err.max();   loss = mean(err if err <= c else (d*d + c*c) / (2*c))     over ALL pixels
+
+    The cutoff ``c`` depends on the data and carries a gradient, into the pixel(s) that hold the maximum.
+
+    fp32 CUDA tensors on one device take ONE fused HIP forward and one fused backward (``cerberus::inv_huber``,
+    ``csrc/depth_loss.hip``); for integer ratios H / h and W / w the kernels read ``gt[b, y*(H/h), x*(W/w)]`` themselves, for
+    any other ratio the ground truth is resized first.  16-bit, 64-bit and CPU tensors, and a ``gt`` that requires grad, take
+    the reference's chain of stock ops.
+
+    The fused op differs from the reference where the reference fails: pixels with ``gt <= 0`` (or NaN) are skipped by
+    selection, so a NaN or an infinity predicted there changes nothing (the reference multiplies by the mask and returns
+    NaN); and ``c == 0`` (no valid pixel, or every valid pixel exact) gives 0 with a zero gradient, the limit of the formula,
+    where the reference divides by ``2*c`` and returns NaN."""
+    pred, gt = _map3(pred, "prediction"), _map3(gt, "ground truth")
+    h, w = pred.shape[1:]
+    H, W = gt.shape[1:]
+    fused = _inv_huber_fusable(pred, gt)
+    if (H, W) != (h, w) and not (fused and H % h == 0 and W % w == 0):
+        gt = _nearest(gt, (h, w))
+    if fused:
+        return torch.ops.cerberus.inv_huber(pred, gt)[0]
+    return _inv_huber_stock(pred, gt)
+
+
+def _depth_pair(predictions, targets):
+    assert 'depth' in predictions.keys() and 'disparity' in targets.keys()
+    return predictions['depth'], targets['disparity']
+
+
+def _check_backend(backend):
+    if backend not in ("hip", "torch"):
+        raise ValueError("backend must be 'hip' or 'torch'")
+    return backend
+
+
+class InvHuberLoss(torch.nn.Module):
+    """Inverse Huber (berHu) loss for depth / disparity training (reference :64-88): ``weight * inv_huber_loss(
+    predictions['depth'], targets['disparity'])``.
+
+    ``backend='hip'`` (default): the fused HIP op for fp32 CUDA tensors (see ``inv_huber_loss``, also for the two corners
+    where it returns a number and the reference NaN).  ``backend='torch'``: the stock-op formulation in the reference's
+    operation order."""
+
+    def __init__(self, weight=1.0, backend="hip", **kwargs):
+        super().__init__()
+        self.weight = weight
+        self.backend = _check_backend(backend)
+
+    def forward(self, predictions, targets):
+        disp_pred, disp_gt = _depth_pair(predictions, targets)
+        if self.backend == "hip":
+            return self.weight * inv_huber_loss(disp_pred, disp_gt)
+        return self.weight * _inv_huber_stock(disp_pred.squeeze(dim=1), disp_gt)
+
+
+class InvHuberLossPyr(torch.nn.Module):
+    """``weight * sum_l lvl_weights[l] * inv_huber_loss(level_l, gt)`` over a list ``predictions['depth']`` of (B,1,h_l,w_l)
+    levels, the ground truth ``targets['disparity']`` (B,H,W) nearest-resized to each level.
+
+    This is the evident intent of the reference's class (:90-110), whose own ``forward`` cannot run: it passes tensors to a
+    ``forward`` that asserts on dict keys, and subtracts a (B,1,h,w) map from a (B,h,w) one.  With ``backend='hip'`` (default)
+    a level whose size divides the ground truth's needs no resized map: the kernels gather.  ``backend='torch'``: the stock
+    chain on the resized ground truth."""
+
+    def __init__(self, lvl_weights, weight=1.0, backend="hip", **kwargs):
+        super().__init__()
+        self.lvl_weights = lvl_weights
+        self.weight = weight
+        self.backend = _check_backend(backend)
+
+    def forward(self, predictions, targets):
+        disp_pred, disp_gt = _depth_pair(predictions, targets)
+        loss = 0
+        for lvl, pred in enumerate(disp_pred):
+            if self.backend == "hip":
+                lvl_loss = inv_huber_loss(pred, disp_gt)
+            else:
+                lvl_loss = _inv_huber_stock(pred.squeeze(dim=1), _nearest(disp_gt, pred.size()[2:]))
+            loss = loss + lvl_loss * self.lvl_weights[lvl]
+        return self.weight * loss
+
+
+def _positive_prediction(disp_pred):
+    """The reference's ``relu`` and ``disp_pred[disp_pred == 0] += 0.001`` (:27-28, :54-55) out of place: the in-place form on
+    the output of relu makes the reference's backward raise."""
+    disp_pred = F.relu(disp_pred.squeeze(dim=1))
+    return torch.where(disp_pred > 0, disp_pred, 0.001)
+
+
+class ScaleInvariantError(torch.nn.Module):
+    """Scale-invariant log error over the pixels with ``gt > 0`` (reference :42-62), in stock ops.
+
+    A restatement that can be trained with: the reference's in-place ``+= 0.001`` makes its backward raise, and its
+    boolean-mask indexing synchronises with the host.  Here the mask is applied with ``torch.where`` and a valid count: the
+    same forward value, differentiable, capturable.  Not on the HIP path: no reference config trains with it."""
+
+    def __init__(self, weight=1.0, lmda=1, **kwargs):
+        super().__init__()
+        self.lmda = lmda
+        self.weight = weight
+
+    def forward(self, predictions, targets):
+        disp_pred, disp_gt = _depth_pair(predictions, targets)
+        disp_pred = _positive_prediction(disp_pred)
+        mask = disp_gt > 0
+        count = mask.sum()
+        log_diff = torch.where(mask, torch.log(disp_pred) - torch.log(torch.where(mask, disp_gt, 1.0)), 0.0)
+        element_wise = torch.pow(log_diff, 2).sum() / count
+        scaled_error = self.lmda * (log_diff.sum()**2) / (count**2)
+        return self.weight * (element_wise - scaled_error)
+
+
+class DepthAwareLoss(torch.nn.Module):
+    """Depth-aware smooth-L1 loss over the pixels with ``gt > 0`` (reference :16-40), in stock ops.
+
+    A restatement that can be trained with, as ``ScaleInvariantError``: the ``+ 0.001`` out of place, ``torch.where`` and a
+    valid count instead of boolean-mask indexing.  Not on the HIP path: no reference config trains with it."""
+
+    def __init__(self, weight=1.0, **kwargs):
+        super().__init__()
+        self.weight = weight
+
+    def forward(self, predictions, targets):
+        disp_pred, disp_gt = _depth_pair(predictions, targets)
+        disp_pred = _positive_prediction(disp_pred)
+        mask = disp_gt > 0
+        count = mask.sum()
+        safe_gt = torch.where(mask, disp_gt, 2.0)      # log(2) != 0: no 0 / 0 in the ratio below, whose backward would give NaN
+        l_disp_pred = torch.log(disp_pred)
+        l_disp_gt = torch.log(safe_gt)
+        regularization = 1 - torch.min(l_disp_pred, l_disp_gt) / torch.max(l_disp_pred, l_disp_gt)
+        l_loss = torch.where(mask, F.smooth_l1_loss(disp_pred, safe_gt, reduction='none'), 0.0).sum() / count
+        depth_aware_attention = disp_gt / torch.where(mask, disp_gt, -float("inf")).max()
+        return self.weight * torch.where(mask, (depth_aware_attention + regularization) * l_loss, 0.0).sum() / count

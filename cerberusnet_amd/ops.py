@@ -73,6 +73,8 @@ _def.define("seg_cross_entropy(Tensor logits, Tensor target, Tensor weight, int 
 _def.define("seg_cross_entropy_backward(Tensor logits, Tensor target, Tensor weight, Tensor lse, Tensor state, Tensor grad_loss, "
             "int ignore_index) -> Tensor")
 _def.define("class_histogram(Tensor target, int num_classes, int ignore_index) -> Tensor")
+_def.define("inv_huber(Tensor pred, Tensor gt) -> (Tensor loss, Tensor state)")
+_def.define("inv_huber_backward(Tensor pred, Tensor gt, Tensor state, Tensor grad_loss) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -967,6 +969,82 @@ def _class_histogram_cuda(target, num_classes, ignore_index):
     return counts
 
 
+# the supervised depth loss InvHuberLoss (depth_losses.py:64-88), csrc/depth_loss.hip
+INV_HUBER_CHUNK_PIXELS = 1024           # pixels per workgroup of the sum pass: a partial of sum(term), of S and of ties each
+INV_HUBER_MAX_PARTS = 1024              # partial maxima of the max pass
+
+
+def _inv_huber_workspace_bytes(B, h, w):
+    """cerberus_inv_huber_workspace_bytes in pure Python (a test holds the two equal): 1024 partial maxima, then an fp32
+    sum(term), an fp32 S and a uint32 ties partial per 1024 pixels of the flattened (B,h,w) prediction."""
+    if B <= 0 or h <= 0 or w <= 0 or B * h * w > 0x7fffffff - 1024:
+        return 0
+    return (INV_HUBER_MAX_PARTS + 3 * ((B * h * w + INV_HUBER_CHUNK_PIXELS - 1) // INV_HUBER_CHUNK_PIXELS)) * 4
+
+
+def _inv_huber_check(pred, gt, what):
+    """(B, h, w, H, W) of a prediction (B,1,h,w) or (B,h,w) and a ground truth (B,H,W) the op takes."""
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        shape = (pred.shape[0],) + tuple(pred.shape[2:])
+    elif pred.dim() == 3:
+        shape = tuple(pred.shape)
+    else:
+        raise RuntimeError("%s: pred must be (B,1,h,w) or (B,h,w), got %s" % (what, tuple(pred.shape)))
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise RuntimeError("%s: pred and gt must be float32, got %s and %s (16-bit and 64-bit tensors take the stock-op path "
+                           "of loss_functions.inv_huber_loss)" % (what, pred.dtype, gt.dtype))
+    if gt.device != pred.device:
+        raise RuntimeError("%s: inputs on different devices: %s, %s" % (what, pred.device, gt.device))
+    if gt.dim() != 3 or gt.shape[0] != shape[0]:
+        raise RuntimeError("%s: gt must be (B,H,W) with B = %d, got %s" % (what, shape[0], tuple(gt.shape)))
+    B, h, w = shape
+    H, W = gt.shape[1:]
+    if pred.numel() == 0 or gt.numel() == 0:
+        raise RuntimeError("%s: needs at least one pixel, got %s and %s" % (what, tuple(pred.shape), tuple(gt.shape)))
+    if H % h != 0 or W % w != 0:
+        raise RuntimeError("%s: the gt size %s must be an integer multiple of the prediction's %s (loss_functions.inv_huber_loss "
+                           "resizes the ground truth for any other ratio)" % (what, (H, W), (h, w)))
+    if B * h * w > 0x7fffffff - 1024:
+        raise RuntimeError("%s: %d pixels do not fit the kernels' 32-bit pixel index" % (what, B * h * w))
+    return B, h, w, H, W
+
+
+def _inv_huber_cuda(pred, gt):
+    what = "cerberus::inv_huber"
+    B, h, w, H, W = _inv_huber_check(pred, gt, what)
+    p, g = pred.contiguous(), gt.contiguous()
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_inv_huber_workspace_bytes(B, h, w)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=p.device)
+    loss = torch.empty((), dtype=torch.float32, device=p.device)
+    state = torch.empty((4,), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        rc = lib.cerberus_inv_huber_forward(p.data_ptr(), g.data_ptr(), loss.data_ptr(), state.data_ptr(), ws.data_ptr(), ws_bytes,
+                                            B, h, w, H, W, 0, _stream_ptr(p))
+    _lib.check(rc, what)
+    return loss, state
+
+
+def _inv_huber_meta(pred, gt):
+    return pred.new_empty((), dtype=torch.float32), pred.new_empty((4,), dtype=torch.float32)
+
+
+def _inv_huber_backward_cuda(pred, gt, state, grad_loss):
+    what = "cerberus::inv_huber_backward"
+    B, h, w, H, W = _inv_huber_check(pred, gt, what)
+    if state.dtype != torch.float32 or state.device != pred.device or tuple(state.shape) != (4,):
+        raise RuntimeError("%s: state must be the float32 (4,) tensor of the forward, got %s %s" % (what, state.dtype,
+                                                                                                   tuple(state.shape)))
+    p, g = pred.contiguous(), gt.contiguous()
+    gl = _grad_scalar(grad_loss, p, what)
+    grad = torch.empty_like(p)          # every element is written by the kernel
+    with torch.cuda.device(p.device):
+        rc = _lib.get().cerberus_inv_huber_backward(p.data_ptr(), g.data_ptr(), state.contiguous().data_ptr(), gl.data_ptr(),
+                                                    grad.data_ptr(), B, h, w, H, W, 0, _stream_ptr(p))
+    _lib.check(rc, what)
+    return grad
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -1022,6 +1100,12 @@ _def.impl("class_histogram", _no_cpu("class_histogram"), "CPU")
 _def.impl("edge_smoothness", _edge_smoothness_cuda, "CUDA")
 _def.impl("edge_smoothness", lambda f, i, al, d: f.new_empty((), dtype=torch.float32), "Meta")
 _def.impl("edge_smoothness", _no_cpu("edge_smoothness"), "CPU")
+_def.impl("inv_huber", _inv_huber_cuda, "CUDA")
+_def.impl("inv_huber", _inv_huber_meta, "Meta")
+_def.impl("inv_huber", _no_cpu("inv_huber"), "CPU")
+_def.impl("inv_huber_backward", _inv_huber_backward_cuda, "CUDA")
+_def.impl("inv_huber_backward", lambda p, g, st, gl: torch.empty_like(p), "Meta")
+_def.impl("inv_huber_backward", _no_cpu("inv_huber_backward"), "CPU")
 _def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
 _def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
 _def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
@@ -1276,6 +1360,23 @@ def _seg_backward(ctx, grad_loss, _grad_lse, _grad_state):
     return gx, None, None, None, None
 
 
+def _inv_huber_setup(ctx, inputs, output):
+    pred, gt = inputs
+    _loss, state = output
+    # the inputs and the four scalars the forward left on the device: the backward recomputes every pixel's terms
+    ctx.save_for_backward(pred, gt, state)
+    ctx.mark_non_differentiable(state)
+
+
+def _inv_huber_backward(ctx, grad_loss, _grad_state):
+    pred, gt, state = ctx.saved_tensors
+    if ctx.needs_input_grad[1]:
+        raise RuntimeError("cerberus::inv_huber has no gradient for the ground truth: loss_functions.inv_huber_loss takes the "
+                           "stock-op path for a gt that requires grad")
+    gp = torch.ops.cerberus.inv_huber_backward(pred, gt, state, grad_loss) if ctx.needs_input_grad[0] else None
+    return gp, None
+
+
 def _histogram_backward(ctx, grad):
     raise RuntimeError("cerberus::class_histogram is not differentiable: it counts integer labels")
 
@@ -1302,3 +1403,6 @@ torch.library.register_autograd("cerberus::seg_cross_entropy", _seg_backward, se
 torch.library.register_autograd("cerberus::seg_cross_entropy_backward", _no_double_backward("seg_cross_entropy_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::class_histogram", _histogram_backward, setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::inv_huber", _inv_huber_backward, setup_context=_inv_huber_setup)
+torch.library.register_autograd("cerberus::inv_huber_backward", _no_double_backward("inv_huber_backward"),
+                                setup_context=lambda ctx, inputs, output: None)

@@ -421,6 +421,37 @@ int cerberus_seg_cross_entropy_backward(const void *logits, const void *target, 
 int cerberus_class_histogram(const void *target, void *counts, int64_t count, int num_classes,
                              int64_t ignore_index, void *stream);
 
+/* The supervised depth loss InvHuberLoss (berHu) as one differentiable scalar (additions only: no ABI bump): the reference's
+ * InvHuberLoss.forward (depth_losses.py:64-88) without `weight`, fp32.
+ *   pred : (B,h,w) (a (B,1,h,w) prediction is the same memory);  gt : (B,H,W) with H % h == 0 and W % w == 0.  Pixel (y, x) of
+ *          the prediction is compared with gt[b, y * (H / h), x * (W / w)]: for H == h, W == w the same pixel, otherwise the
+ *          pixel F.interpolate(gt, (h, w), mode='nearest') picks (a pyramid level without a resized map).
+ *   valid = g > 0 (false for a NaN g);  d = max(p, 0) - g;  err = valid ? |d| : 0;  m = max err;  c = 0.2 m;  N = B h w
+ *   loss[0] = sum(err > c ? (d d + c c) / (2 c) : err) / N  -- N counts ALL pixels, as the reference's mean
+ *   S = sum over {err > c} of (1/2 - d d / (2 c c));  ties = #{err == m}
+ *   state : 4 floats, overwritten: [c, 0.2 S / ties, 1 / N, m], read by the backward on the device
+ *   workspace : cerberus_inv_huber_workspace_bytes(B,h,w) bytes (1024 partial maxima and three partials per 1024 pixels; 0 for
+ *          a non-positive or too large size), 16-byte aligned; no zero-fill needed
+ * Forward: a max pass (at most 1024 workgroups, one partial maximum each; maxima are taken on the bit pattern, where a
+ * positive NaN sorts above infinity), a sum pass that folds those partials itself, and a single-workgroup fixed-order finish:
+ * no atomics, nothing zeroed, no workgroup waits for another, bit-reproducible for a given shape.  A lane owns 4 consecutive
+ * pixels and loads 16 bytes of each map when h*w % 4 == 0, H == h, W == w and pred and gt are 16-byte aligned; one pixel per
+ * lane otherwise -- both routes give the same bits.
+ * Backward: grad_pred (B,h,w) = grad_loss[0] / N * [valid and p > 0] ((err > c ? d / c : sign(d)) + [err == m] state[1] sign(d)),
+ * every element written exactly once (no zero-fill).  The second summand is the gradient through the data-dependent cutoff c,
+ * split evenly over the pixels that hold the maximum.  grad_loss points to ONE float in DEVICE memory (capturable).
+ * Decided by selection: an invalid pixel adds nothing whatever pred holds there and its gradient is 0.0f; a NaN at a valid
+ * pixel gives a NaN loss; c == 0 (no valid pixel, or every valid pixel exact) gives loss 0.0f and a gradient of zeros (the
+ * reference divides by 2 c and returns NaN); p <= 0 has gradient 0.0f.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0 or a size <= 0 CERB_EINVAL; H % h != 0 or
+ * W % w != 0 CERB_EUNSUPPORTED; B*h*w > 2^31 - 1025 CERB_ETOOLARGE; then B == 0 returns 0 without a launch; a null pointer, a
+ * workspace that is misaligned or too small CERB_EINVAL -- all before any launch. */
+int64_t cerberus_inv_huber_workspace_bytes(int B, int h, int w);
+int cerberus_inv_huber_forward(const void *pred, const void *gt, void *loss, void *state, void *workspace,
+                               int64_t workspace_bytes, int B, int h, int w, int H, int W, int dtype, void *stream);
+int cerberus_inv_huber_backward(const void *pred, const void *gt, const void *state, const void *grad_loss,
+                                void *grad_pred, int B, int h, int w, int H, int W, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
