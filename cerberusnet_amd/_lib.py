@@ -60,6 +60,13 @@ PROTOTYPES = {
     "cerberus_inv_huber_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_inv_huber_forward": (_I, [_P] * 5 + [_I64] + [_I] * 6 + [_P]),
     "cerberus_inv_huber_backward": (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    "cerberus_seg_confusion": (_I, [_P] * 3 + [_I] * 4 + [_I64, _I, _P]),
+    "cerberus_depth_metric_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_depth_metric_sums": (_I, [_P] * 5 + [_I64] + [_I] * 3 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_flow_metric_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_flow_metric_sums": (_I, [_P] * 6 + [_I64] + [_I] * 4 + [_P]),
+    "cerberus_warp_sad_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_warp_sad": (_I, [_P] * 5 + [_I64] + [_I] * 5 + [_P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

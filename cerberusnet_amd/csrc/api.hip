@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
-// census.hip, occlusion.hip, reproject.hip, seg_loss.hip and depth_loss.hip.
+// census.hip, occlusion.hip, reproject.hip, seg_loss.hip, depth_loss.hip and metrics.hip.
 #include <atomic>
 #include <cstring>
 
@@ -520,6 +520,78 @@ int cerberus_inv_huber_backward(const void *pred, const void *gt, const void *st
     if (B == 0) return CERB_OK;
     if (!pred || !gt || !state || !grad_loss || !grad_pred) return CERB_EINVAL;
     return inv_huber_backward(pred, gt, state, grad_loss, grad_pred, B, h, w, H, W, static_cast<hipStream_t>(stream));
+}
+
+// the training metrics: one image's pixels are counted with an int (a workgroup's last pixel index may run 1023 past the end
+// before it is tested), the image is the launch grid's second dimension; offsets into the tensors are 64-bit.
+static int metric_args_ok(int B, int C, int H, int W, int min_channels, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B < 0 || C < min_channels || H <= 0 || W <= 0) return CERB_EINVAL;
+    if (static_cast<int64_t>(H) * W > 0x7fffffff - 1024 || B > 65535) return CERB_ETOOLARGE;
+    return CERB_OK;
+}
+
+static bool metric_size_ok(int B, int H, int W) {
+    return B > 0 && B <= 65535 && H > 0 && W > 0 && static_cast<int64_t>(H) * W <= 0x7fffffff - 1024;
+}
+
+static int metric_workspace_ok(const void *workspace, int64_t have, int64_t need) {
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 7) || have < need) return CERB_EINVAL;
+    return CERB_OK;
+}
+
+int cerberus_seg_confusion(const void *logits, const void *target, void *confusion, int B, int C, int H, int W, int64_t ignore_index,
+                           int dtype, void *stream) {
+    const int rc = metric_args_ok(B, C, H, W, 2, dtype);
+    if (rc) return rc;
+    if (C > seg_confusion_max_classes()) return CERB_EUNSUPPORTED;          // the C*C bins of a workgroup live in LDS
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !confusion) return CERB_EINVAL;
+    return seg_confusion(logits, target, confusion, B, C, H, W, ignore_index, static_cast<hipStream_t>(stream));
+}
+
+int64_t cerberus_depth_metric_workspace_bytes(int B, int h, int w) {
+    return metric_size_ok(B, h, w) ? depth_metric_workspace_bytes(B, h, w) : 0;
+}
+
+int cerberus_depth_metric_sums(const void *pred, const void *gt, void *sums, void *counts, void *workspace, int64_t workspace_bytes,
+                               int B, int h, int w, float min_depth, float max_depth, int dtype, void *stream) {
+    const int rc = metric_args_ok(B, 1, h, w, 1, dtype);
+    if (rc) return rc;
+    if (!(min_depth < max_depth)) return CERB_EINVAL;                     // a NaN bound too
+    if (B == 0) return CERB_OK;
+    if (!pred || !gt || !sums || !counts) return CERB_EINVAL;
+    if (metric_workspace_ok(workspace, workspace_bytes, depth_metric_workspace_bytes(B, h, w))) return CERB_EINVAL;
+    return depth_metric_sums(pred, gt, sums, counts, workspace, B, h, w, min_depth, max_depth, static_cast<hipStream_t>(stream));
+}
+
+int64_t cerberus_flow_metric_workspace_bytes(int B, int H, int W) {
+    return metric_size_ok(B, H, W) ? flow_metric_workspace_bytes(B, H, W) : 0;
+}
+
+int cerberus_flow_metric_sums(const void *flow_pred, const void *flow_gt, const void *mask, void *sums, void *counts, void *workspace,
+                              int64_t workspace_bytes, int B, int H, int W, int dtype, void *stream) {
+    const int rc = metric_args_ok(B, 2, H, W, 2, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!flow_pred || !flow_gt || !mask || !sums || !counts) return CERB_EINVAL;
+    if (metric_workspace_ok(workspace, workspace_bytes, flow_metric_workspace_bytes(B, H, W))) return CERB_EINVAL;
+    return flow_metric_sums(flow_pred, flow_gt, mask, sums, counts, workspace, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+int64_t cerberus_warp_sad_workspace_bytes(int B, int H, int W) {
+    return metric_size_ok(B, H, W) ? warp_sad_workspace_bytes(B, H, W) : 0;
+}
+
+int cerberus_warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace, int64_t workspace_bytes,
+                      int B, int C, int H, int W, int dtype, void *stream) {
+    const int rc = metric_args_ok(B, C, H, W, 1, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!image || !source || !flow || !sad) return CERB_EINVAL;
+    if (metric_workspace_ok(workspace, workspace_bytes, warp_sad_workspace_bytes(B, H, W))) return CERB_EINVAL;
+    return warp_sad(image, source, flow, sad, workspace, B, C, H, W, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

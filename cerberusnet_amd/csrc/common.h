@@ -264,6 +264,22 @@ int inv_huber_forward(const void *pred, const void *gt, void *loss, void *state,
 int inv_huber_backward(const void *pred, const void *gt, const void *state, const void *grad_loss, void *grad_pred, int B, int h, int w,
                        int H, int W, hipStream_t s);
 
+// metrics.hip: the per-image statistics of the training metrics, fp32 inputs, forward only; arguments are checked by api.hip.
+// confusion: (B,C,C) int64, zeroed on the stream by the call; sums: float64, counts: int64, one row per image; `workspace` is
+// 8-byte aligned and needs no zero-fill.
+int seg_confusion_max_classes();
+int seg_confusion(const void *logits, const void *target, void *confusion, int B, int C, int H, int W, int64_t ignore_index,
+                  hipStream_t s);
+int64_t depth_metric_workspace_bytes(int B, int h, int w);
+int depth_metric_sums(const void *pred, const void *gt, void *sums, void *counts, void *workspace, int B, int h, int w, float min_depth,
+                      float max_depth, hipStream_t s);
+int64_t flow_metric_workspace_bytes(int B, int H, int W);
+int flow_metric_sums(const void *flow_pred, const void *flow_gt, const void *mask, void *sums, void *counts, void *workspace, int B,
+                     int H, int W, hipStream_t s);
+int64_t warp_sad_workspace_bytes(int B, int H, int W);
+int warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace, int B, int C, int H, int W,
+             hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

@@ -75,6 +75,10 @@ _def.define("seg_cross_entropy_backward(Tensor logits, Tensor target, Tensor wei
 _def.define("class_histogram(Tensor target, int num_classes, int ignore_index) -> Tensor")
 _def.define("inv_huber(Tensor pred, Tensor gt) -> (Tensor loss, Tensor state)")
 _def.define("inv_huber_backward(Tensor pred, Tensor gt, Tensor state, Tensor grad_loss) -> Tensor")
+_def.define("seg_confusion(Tensor logits, Tensor target, int ignore_index) -> Tensor")
+_def.define("depth_metric_sums(Tensor pred, Tensor gt, float min_depth, float max_depth) -> (Tensor sums, Tensor counts)")
+_def.define("flow_metric_sums(Tensor flow_pred, Tensor flow_gt, Tensor mask) -> (Tensor sums, Tensor counts)")
+_def.define("warp_sad(Tensor image, Tensor source, Tensor flow) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -1045,6 +1049,153 @@ def _inv_huber_backward_cuda(pred, gt, state, grad_loss):
     return grad
 
 
+# the training metrics (nnet_training/statistics/), csrc/metrics.hip
+METRIC_CHUNK_PIXELS = 1024              # pixels of ONE image per workgroup: a partial per sum and count each
+SEG_CONFUSION_MAX_CLASSES = 64          # C*C 32-bit LDS bins (16 KiB); more classes: the stock chain in statistics.SegmentationMetric
+METRIC_MAX_BATCH = 65535                # the image is the launch grid's second dimension
+
+
+def _metric_workspace_bytes(B, H, W, nsums, ncounts):
+    if B <= 0 or B > METRIC_MAX_BATCH or H <= 0 or W <= 0 or H * W > 0x7fffffff - 1024:
+        return 0
+    return B * ((H * W + METRIC_CHUNK_PIXELS - 1) // METRIC_CHUNK_PIXELS) * (8 * nsums + 4 * ncounts)
+
+
+def _depth_metric_workspace_bytes(B, h, w):
+    """cerberus_depth_metric_workspace_bytes in pure Python (a test holds the two equal): five float64 sums and four uint32
+    counts per 1024 pixels of each image."""
+    return _metric_workspace_bytes(B, h, w, 5, 4)
+
+
+def _flow_metric_workspace_bytes(B, H, W):
+    """cerberus_flow_metric_workspace_bytes in pure Python: two float64 sums and one uint32 count per 1024 pixels of each image."""
+    return _metric_workspace_bytes(B, H, W, 2, 1)
+
+
+def _warp_sad_workspace_bytes(B, H, W):
+    """cerberus_warp_sad_workspace_bytes in pure Python: one float64 sum per 1024 pixels of each image."""
+    return _metric_workspace_bytes(B, H, W, 1, 0)
+
+
+def _metric_check(what, tensors, shapes, dtypes=None):
+    """Every (name, tensor) of ``tensors`` is on the first one's device, has the shape of ``shapes`` and is float32 (or the
+    dtype of ``dtypes``); the batch and the image fit the launch grid."""
+    first = tensors[0][1]
+    for i, (name, t) in enumerate(tensors):
+        want = (dtypes or {}).get(name, torch.float32)
+        if t.dtype != want:
+            raise RuntimeError("%s: %s must be %s, got %s (other dtypes take the stock-op path of cerberusnet_amd.statistics)"
+                               % (what, name, str(want).replace("torch.", ""), t.dtype))
+        if t.device != first.device:
+            raise RuntimeError("%s: inputs on different devices: %s, %s" % (what, first.device, t.device))
+        if tuple(t.shape) != tuple(shapes[i]):
+            raise RuntimeError("%s: %s must be %s, got %s" % (what, name, tuple(shapes[i]), tuple(t.shape)))
+    if first.numel() == 0:
+        raise RuntimeError("%s: needs at least one pixel, got %s" % (what, tuple(first.shape)))
+    B, H, W = first.shape[0], first.shape[-2], first.shape[-1]
+    if B > METRIC_MAX_BATCH or H * W > 0x7fffffff - 1024:
+        raise RuntimeError("%s: %d images of %d pixels do not fit the kernels' launch grid" % (what, B, H * W))
+
+
+def _metric_workspace(nbytes, device):
+    return torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=device)     # 8-byte aligned, never zeroed
+
+
+def _seg_confusion_cuda(logits, target, ignore_index):
+    what = "cerberus::seg_confusion"
+    if logits.dim() != 4:
+        raise RuntimeError("%s: logits must be a 4-D (B,C,H,W) tensor, got %s" % (what, tuple(logits.shape)))
+    B, C, H, W = logits.shape
+    _metric_check(what, [("logits", logits), ("target", target)], [(B, C, H, W), (B, H, W)], {"target": torch.int64})
+    if not 2 <= C <= SEG_CONFUSION_MAX_CLASSES:
+        raise RuntimeError("%s: the class count must lie in 2..%d, got %d (statistics.SegmentationMetric takes the stock-op path "
+                           "outside it)" % (what, SEG_CONFUSION_MAX_CLASSES, C))
+    x, t = logits.contiguous(), target.contiguous()
+    conf = torch.empty((B, C, C), dtype=torch.int64, device=x.device)            # zeroed on the stream by the call
+    with torch.cuda.device(x.device):
+        rc = _lib.get().cerberus_seg_confusion(x.data_ptr(), t.data_ptr(), conf.data_ptr(), B, C, H, W, int(ignore_index), 0,
+                                               _stream_ptr(x))
+    _lib.check(rc, what)
+    return conf
+
+
+def _depth_metric_shape(pred, what):
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        return (pred.shape[0],) + tuple(pred.shape[2:])
+    if pred.dim() == 3:
+        return tuple(pred.shape)
+    raise RuntimeError("%s: pred must be (B,1,h,w) or (B,h,w), got %s" % (what, tuple(pred.shape)))
+
+
+def _depth_metric_sums_cuda(pred, gt, min_depth, max_depth):
+    what = "cerberus::depth_metric_sums"
+    B, h, w = _depth_metric_shape(pred, what)
+    _metric_check(what, [("pred", pred), ("gt", gt)], [tuple(pred.shape), (B, h, w)])
+    if not min_depth < max_depth:
+        raise RuntimeError("%s: min_depth %r must lie below max_depth %r" % (what, min_depth, max_depth))
+    p, g = pred.contiguous(), gt.contiguous()
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_depth_metric_workspace_bytes(B, h, w)
+    ws = _metric_workspace(ws_bytes, p.device)
+    sums = torch.empty((B, 5), dtype=torch.float64, device=p.device)
+    counts = torch.empty((B, 4), dtype=torch.int64, device=p.device)
+    with torch.cuda.device(p.device):
+        rc = lib.cerberus_depth_metric_sums(p.data_ptr(), g.data_ptr(), sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws_bytes,
+                                            B, h, w, ctypes.c_float(min_depth), ctypes.c_float(max_depth), 0, _stream_ptr(p))
+    _lib.check(rc, what)
+    return sums, counts
+
+
+def _flow_metric_sums_cuda(flow_pred, flow_gt, mask):
+    what = "cerberus::flow_metric_sums"
+    if flow_pred.dim() != 4 or flow_pred.shape[1] != 2:
+        raise RuntimeError("%s: flow_pred must be a 4-D (B,2,H,W) tensor, got %s" % (what, tuple(flow_pred.shape)))
+    B, _, H, W = flow_pred.shape
+    _metric_check(what, [("flow_pred", flow_pred), ("flow_gt", flow_gt), ("mask", mask)], [(B, 2, H, W), (B, 2, H, W), (B, H, W)])
+    fp, fg, m = flow_pred.contiguous(), flow_gt.contiguous(), mask.contiguous()
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_flow_metric_workspace_bytes(B, H, W)
+    ws = _metric_workspace(ws_bytes, fp.device)
+    sums = torch.empty((B, 2), dtype=torch.float64, device=fp.device)
+    counts = torch.empty((B, 1), dtype=torch.int64, device=fp.device)
+    with torch.cuda.device(fp.device):
+        rc = lib.cerberus_flow_metric_sums(fp.data_ptr(), fg.data_ptr(), m.data_ptr(), sums.data_ptr(), counts.data_ptr(),
+                                           ws.data_ptr(), ws_bytes, B, H, W, 0, _stream_ptr(fp))
+    _lib.check(rc, what)
+    return sums, counts
+
+
+def _warp_sad_cuda(image, source, flow):
+    what = "cerberus::warp_sad"
+    if image.dim() != 4:
+        raise RuntimeError("%s: image must be a 4-D (B,C,H,W) tensor, got %s" % (what, tuple(image.shape)))
+    B, C, H, W = image.shape
+    _metric_check(what, [("image", image), ("source", source), ("flow", flow)], [(B, C, H, W), (B, C, H, W), (B, 2, H, W)])
+    im, src, fl = image.contiguous(), source.contiguous(), flow.contiguous()
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_warp_sad_workspace_bytes(B, H, W)
+    ws = _metric_workspace(ws_bytes, im.device)
+    sad = torch.empty((B,), dtype=torch.float64, device=im.device)
+    with torch.cuda.device(im.device):
+        rc = lib.cerberus_warp_sad(im.data_ptr(), src.data_ptr(), fl.data_ptr(), sad.data_ptr(), ws.data_ptr(), ws_bytes, B, C, H, W,
+                                   0, _stream_ptr(im))
+    _lib.check(rc, what)
+    return sad
+
+
+def _seg_confusion_meta(logits, target, ignore_index):
+    return logits.new_empty((logits.shape[0], logits.shape[1], logits.shape[1]), dtype=torch.int64)
+
+
+def _depth_metric_sums_meta(pred, gt, min_depth, max_depth):
+    return pred.new_empty((pred.shape[0], 5), dtype=torch.float64), pred.new_empty((pred.shape[0], 4), dtype=torch.int64)
+
+
+def _flow_metric_sums_meta(flow_pred, flow_gt, mask):
+    B = flow_pred.shape[0]
+    return flow_pred.new_empty((B, 2), dtype=torch.float64), flow_pred.new_empty((B, 1), dtype=torch.int64)
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -1106,6 +1257,18 @@ _def.impl("inv_huber", _no_cpu("inv_huber"), "CPU")
 _def.impl("inv_huber_backward", _inv_huber_backward_cuda, "CUDA")
 _def.impl("inv_huber_backward", lambda p, g, st, gl: torch.empty_like(p), "Meta")
 _def.impl("inv_huber_backward", _no_cpu("inv_huber_backward"), "CPU")
+_def.impl("seg_confusion", _seg_confusion_cuda, "CUDA")
+_def.impl("seg_confusion", _seg_confusion_meta, "Meta")
+_def.impl("seg_confusion", _no_cpu("seg_confusion"), "CPU")
+_def.impl("depth_metric_sums", _depth_metric_sums_cuda, "CUDA")
+_def.impl("depth_metric_sums", _depth_metric_sums_meta, "Meta")
+_def.impl("depth_metric_sums", _no_cpu("depth_metric_sums"), "CPU")
+_def.impl("flow_metric_sums", _flow_metric_sums_cuda, "CUDA")
+_def.impl("flow_metric_sums", _flow_metric_sums_meta, "Meta")
+_def.impl("flow_metric_sums", _no_cpu("flow_metric_sums"), "CPU")
+_def.impl("warp_sad", _warp_sad_cuda, "CUDA")
+_def.impl("warp_sad", lambda im, src, fl: im.new_empty((im.shape[0],), dtype=torch.float64), "Meta")
+_def.impl("warp_sad", _no_cpu("warp_sad"), "CPU")
 _def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
 _def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
 _def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
@@ -1381,6 +1544,13 @@ def _histogram_backward(ctx, grad):
     raise RuntimeError("cerberus::class_histogram is not differentiable: it counts integer labels")
 
 
+def _metric_backward(name):
+    def _raise(ctx, *grads):
+        raise RuntimeError("cerberus::%s is not differentiable: it is a training metric (counts and per-image sums for the "
+                           "logger), not a loss" % name)
+    return _raise
+
+
 def _no_double_backward(name):
     def _raise(ctx, *grads):
         raise RuntimeError("cerberus::%s is not differentiable (no double backward)" % name)
@@ -1406,3 +1576,5 @@ torch.library.register_autograd("cerberus::class_histogram", _histogram_backward
 torch.library.register_autograd("cerberus::inv_huber", _inv_huber_backward, setup_context=_inv_huber_setup)
 torch.library.register_autograd("cerberus::inv_huber_backward", _no_double_backward("inv_huber_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
+for _name in ("seg_confusion", "depth_metric_sums", "flow_metric_sums", "warp_sad"):
+    torch.library.register_autograd("cerberus::" + _name, _metric_backward(_name), setup_context=lambda ctx, inputs, output: None)

@@ -452,6 +452,55 @@ int cerberus_inv_huber_forward(const void *pred, const void *gt, void *loss, voi
 int cerberus_inv_huber_backward(const void *pred, const void *gt, const void *state, const void *grad_loss,
                                 void *grad_pred, int B, int h, int w, int H, int W, int dtype, void *stream);
 
+/* The per-image statistics of the training metrics (additions only: no ABI bump): what the reference's metric loggers
+ * (nnet_training/statistics/semantic.py, depth.py, optical_flow.py) compute from the model's outputs after every step.  Forward
+ * only, fp32 inputs, everything reduced PER IMAGE.  A workgroup owns 1024 consecutive pixels of one image and a lane 4 of them:
+ * 16-byte loads when H*W % 4 == 0 and the pointers are 16-byte aligned, guarded 4-byte loads otherwise -- both routes give the
+ * same bits.  Terms are fp32 as the reference's element-wise ops and accumulated in float64 from the lane upward; per-workgroup
+ * partials go to `workspace` (8-byte aligned, no zero-fill; its size comes from the *_workspace_bytes function, 0 for a
+ * non-positive or too large size) and one workgroup per image adds them in a fixed order: no floating-point atomics, no host
+ * round trip, capturable, bit-reproducible for a given shape.
+ *
+ * cerberus_seg_confusion: logits (B,C,H,W) fp32, target (B,H,W) int64 -> confusion (B,C,C) int64, [b, t, p] = the pixels of image
+ *   b with label t whose argmax over the class planes is p (torch.argmax's rule: the first maximal class wins, a NaN logit counts
+ *   as the maximum and the first NaN wins).  No index map is written.  A pixel whose label equals ignore_index or lies outside
+ *   [0, C) is skipped by selection and never forms an address.  `confusion` is zeroed on the stream by the call itself (a kernel)
+ *   and added to with integer adds (32-bit LDS bins per workgroup, one 64-bit global add per non-empty bin): any order, the same
+ *   matrix.  2 <= C <= 64 (16 KiB of LDS bins); more classes: CERB_EUNSUPPORTED.
+ *
+ * cerberus_depth_metric_sums: pred, gt (B,h,w) fp32 (a (B,1,h,w) prediction is the same memory).  A pixel is valid if
+ *   min_depth < gt < max_depth.  p = pred == 0 ? 1e-7f : pred (the input is not written);  d = p - gt;  l = logf(p) - logf(gt);
+ *   r = max(p / gt, gt / p).
+ *   sums   : (B,5) float64, over the valid pixels: |d| / gt, d d / gt, d d, l l, |l|
+ *   counts : (B,4) int64, over the valid pixels: 1, r < 1.25, r < 1.5625, r < 1.953125
+ *   An invalid pixel adds nothing whatever pred holds there; a valid pixel with pred < 0 makes the log sums NaN, as the reference.
+ *
+ * cerberus_flow_metric_sums: flow_pred, flow_gt (B,2,H,W), mask (B,H,W) fp32.  epe = sqrtf(dx dx + dy dy), e = epe * mask.
+ *   sums   : (B,2) float64: sum e, sum mask
+ *   counts : (B,1) int64: the pixels with e > 3 and e / max(|flow_gt|, 1e-10f) > 0.05f
+ *
+ * cerberus_warp_sad: image, source (B,C,H,W), flow (B,2,H,W) fp32 -> sad (B,) float64 = sum over c, y, x of
+ *   |image - flow_warp(source, flow)| with border padding and bilinear sampling: each sample is the element
+ *   cerberus_flow_warp_forward would have written (the same positions, weights and order of products); the warped image is
+ *   never stored.  Any C >= 1.
+ *
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, a size <= 0, C < 2 (seg_confusion) or < 1
+ * (warp_sad), min_depth >= max_depth or NaN CERB_EINVAL; H*W > 2^31 - 1025 or B > 65535 CERB_ETOOLARGE; C > 64 (seg_confusion)
+ * CERB_EUNSUPPORTED; then B == 0 returns 0 without a launch; a null pointer, a workspace that is misaligned or too small
+ * CERB_EINVAL -- all before any launch. */
+int cerberus_seg_confusion(const void *logits, const void *target, void *confusion, int B, int C, int H, int W,
+                           int64_t ignore_index, int dtype, void *stream);
+int64_t cerberus_depth_metric_workspace_bytes(int B, int h, int w);
+int cerberus_depth_metric_sums(const void *pred, const void *gt, void *sums, void *counts, void *workspace,
+                               int64_t workspace_bytes, int B, int h, int w, float min_depth, float max_depth,
+                               int dtype, void *stream);
+int64_t cerberus_flow_metric_workspace_bytes(int B, int H, int W);
+int cerberus_flow_metric_sums(const void *flow_pred, const void *flow_gt, const void *mask, void *sums, void *counts,
+                              void *workspace, int64_t workspace_bytes, int B, int H, int W, int dtype, void *stream);
+int64_t cerberus_warp_sad_workspace_bytes(int B, int H, int W);
+int cerberus_warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace,
+                      int64_t workspace_bytes, int B, int C, int H, int W, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
