@@ -28,6 +28,9 @@
 // Labels never form an address unless they lie in [0, C): an out-of-range label that is not the ignore label adds NaN to
 // num (stock PyTorch raises a device-side assertion there) and gets a zero gradient.  An ignored pixel is skipped by
 // selection: a NaN logit there changes nothing, and its gradient is 0.0f whatever the upstream gradient holds.
+// Logits of -inf (classes switched off) may sit anywhere in a pixel that keeps a finite one: lse is that of the others and
+// their gradient is 0.0f.  A counted pixel whose loss is not finite (its target at -inf, every logit -inf, a +inf logit) makes
+// the loss +inf or NaN, never a dropped term.
 #include "common.h"
 #include "loss_reduce.h"
 
@@ -55,8 +58,12 @@ __device__ __forceinline__ Label classify(int64_t t, int64_t ignore, int C) {
 }
 
 // one class plane's value of one pixel: m = max so far, s = sum of exp(x - m) so far.  A NaN x makes s NaN and leaves m.
+// x == m takes d = 0 by a select: for finite values x - m is that same zero (its sign reaches neither fabsf's result nor
+// d > 0), so no finite path changes a bit; for x = m = -inf (a class switched off while every class before it was too) the
+// difference would be inf - inf = NaN, and is now the step "one more term of weight exp(-inf)": m stays -inf, and the
+// first finite x that follows resets s to 1 through e = exp(-inf) = 0.
 __device__ __forceinline__ void lse_step(float x, bool hit, float &m, float &s, float &xt) {
-    const float d = x - m;
+    const float d = x == m ? 0.f : x - m;
     const float e = expf(-fabsf(d));
     s = d > 0.f ? s * e + 1.f : s + e;
     m = fmaxf(m, x);

@@ -13,7 +13,15 @@ sees that pixel only:
 
 Shapes: the smallest at which each route can go wrong.  Scalar route (h*w odd or 2 mod 4, idle lanes): (1,1,1,1), (1,1,5,7),
 (2,1,37,53) (4 workgroups, a ragged last one), (1,1,3,66).  Vector route: (1,1,1,4), (2,1,8,64) (exactly one full workgroup),
-(3,1,16,33) (odd w: a lane's 4 pixels cross a row).  (2,1,128,256): 64 workgroups, so the partial folds and the finish matter."""
+(3,1,16,33) (odd w: a lane's 4 pixels cross a row).  (2,1,128,256): 64 workgroups, so the partial folds matter; every thread of
+``inv_huber_final_kernel`` still reads at most ONE partial there, and the max pass takes no grid stride.
+
+Past one round (tests/reduction_cases.py, checked on the CPU by tests/test_reduction_tiers_cpu.py; section 11): (1,1,257,1024)
+vector and (1,1,601,1023) scalar, 257 and 601 partials for the finish; (1,1,1025,1024) vector, 1025 chunks on the max pass's 1024
+workgroups (workgroup 0 walks a second chunk; ``fold_parts`` loads its full 1024 partial maxima); (1,1,1537,1023) scalar, 1536
+chunks (half the workgroups walk two); (1,1,6,1000), 6 partial maxima (lane 1 of ``fold_parts`` takes the tail loop); a (1,1,513,512)
+prediction against a (1,1026,1024) ground truth, the gather with 257 partials.  A sum or a maximum over a whole map could hide one
+mis-addressed partial, so the strict maximum is also planted in the first chunk, in 255, 256, 511, 512, 1024 and the last."""
 import functools
 
 import numpy as np
@@ -23,6 +31,7 @@ import torch.nn.functional as F
 
 import cerberusnet_amd as ca
 import depth_loss_cases as cases
+import reduction_cases as rc
 from cerberusnet_amd.loss_functions import depth_losses as D
 from conftest import l2_err, rel_err
 
@@ -112,11 +121,12 @@ def _check_grad(name, fused, stock, ref, at_max):
         assert ef <= GRAD_FACTOR * max(es, GRAD_FLOOR), (name, f, s, r)
 
 
-def _check_case(name, p, g, ref=None):
-    """Fused and stock on the GPU against float64, value and gradient; returns the fused (value, gradient)."""
+def _check_case(name, p, g, ref=None, gt_for_op=None):
+    """Fused and stock on the GPU against float64, value and gradient; returns the fused (value, gradient).  ``gt_for_op``: the
+    finer ground truth that the fused op gathers ``g`` from."""
     ref_v, ref_g = ref if ref is not None else _reference(p, g)
     pd, gd = dev(p), dev(g)
-    v, gr = _fused(pd, gd)
+    v, gr = _fused(pd, gd if gt_for_op is None else dev(gt_for_op))
     vs, gs = _stock(pd, gd)
     assert v.shape == () and v.dtype == torch.float32 and gr.shape == pd.shape and gr.dtype == torch.float32
     _check_value(name, v.item(), vs.item(), ref_v)
@@ -466,3 +476,88 @@ def test_wrapper_takes_the_stock_path_for_what_the_op_does_not_cover():
     gr, = torch.autograd.grad(ca.inv_huber_loss(pp, gd), pp, create_graph=True)
     with pytest.raises(RuntimeError, match="double backward"):
         torch.autograd.grad(gr.sum(), pp)
+
+
+# ---- 11. past one round: 257 to 1536 partials, the max pass's grid stride, both branches of fold_parts ----------------------------
+CASE_IDS = ["x".join(map(str, c[0])) for c in rc.DEPTH_CASES]
+
+
+def _at_prediction(case, g):
+    """(the ground truth a prediction pixel reads, the finer one for the op or None)"""
+    return np.ascontiguousarray(rc.depth_gt_at_prediction(case, g)), (g if rc.depth_route(case) == "gather" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference_of_case(case):
+    p, g = rc.depth_inputs(case)
+    return _reference(p, _at_prediction(case, g)[0])
+
+
+def _state(p, g):
+    return torch.ops.cerberus.inv_huber(dev(p), dev(g))[1]
+
+
+@pytest.mark.parametrize("case", rc.DEPTH_CASES, ids=CASE_IDS)
+def test_table_shapes_against_float64(case):
+    p, g = rc.depth_inputs(case)
+    gp, fine = _at_prediction(case, g)
+    _check_case("inv_huber %s" % (case,), p, gp, _reference_of_case(case), gt_for_op=fine)
+    d = np.maximum(p.reshape(gp.shape), np.float32(0)) - gp
+    m = np.where(gp > 0, np.abs(d), np.float32(0)).max()
+    state = _state(p, g)
+    assert float(state[3]) == float(m) and float(state[0]) == float(np.float32(0.2) * m)
+    assert float(state[2]) == float(np.float32(1) / np.float32(p.size))
+
+
+@pytest.mark.parametrize("case,k", [(c, k) for c in rc.DEPTH_CASES for k in rc.depth_marker_chunks(c)],
+                         ids=["%s-%d" % (i, k) for c, i in zip(rc.DEPTH_CASES, CASE_IDS) for k in rc.depth_marker_chunks(c)])
+def test_the_strict_maximum_in_chunk_k(case, k):
+    """The maximum of err is 20 + 5 k / 64 (its cutoff is exact in fp32: reduction_cases.depth_marker), at one pixel inside chunk k: a chunk that the max pass's stride skips, or a partial
+    maximum that ``fold_parts`` does not read, leaves a maximum below 6."""
+    p, g, pixel, err = rc.depth_marker(case, k)
+    gp, fine = _at_prediction(case, g)
+    _check_case("inv_huber %s maximum in chunk %d" % (case, k), p, gp, gt_for_op=fine)
+    state = _state(p, g)
+    assert float(state[3]) == float(err) and float(state[0]) == float(np.float32(0.2) * err), (float(state[3]), float(err))
+
+
+@pytest.mark.parametrize("case", [c for c in rc.DEPTH_CASES if "inv_huber_max grid stride, %s" % rc.depth_route(c) in rc.depth_tiers(c)],
+                         ids=lambda c: "x".join(map(str, c[0])))
+def test_a_tie_between_chunk_0_and_a_chunk_past_1024(case):
+    p, g, pixels = rc.depth_tie(case)
+    assert pixels[0] < 1024 and pixels[1] // 1024 >= ca.ops.INV_HUBER_MAX_PARTS
+    v, gr = _check_case("inv_huber %s tie" % (case,), p, g)
+    state = _state(p, g)
+    assert float(state[3]) == 19.0 and float(state[0]) == float(np.float32(0.2) * np.float32(19.0))
+    # ties = 2: state[1] = 0.2 S / ties against float64 (every term of S is <= 0: no cancellation)
+    d = np.maximum(p.reshape(g.shape).astype(np.float64), 0) - g
+    err = np.where(g > 0, np.abs(d), 0)
+    c = 0.2 * err.max()
+    share = 0.2 * (0.5 - d[err > c] ** 2 / (2 * c * c)).sum() / 2
+    assert abs(float(state[1]) - share) <= VALUE_TOL * abs(share), (float(state[1]), share)
+    a, b = gr.reshape(-1)[pixels[0]].item(), gr.reshape(-1)[pixels[1]].item()
+    assert a == -b and a != 0                     # split evenly: the same magnitude, the sign of d
+
+
+def test_a_table_shape_twice_and_misaligned_gives_the_same_bits():
+    case = rc.case_of("depth", (1, 1, 1025, 1024))
+    p, g = rc.depth_inputs(case)
+    pa, ga = dev(p), dev(g)
+
+    def shifted(t):
+        buf = torch.zeros(t.numel() + 1, device=DEV)
+        out = buf[1:].view(t.shape)
+        out.copy_(t)
+        return out
+    ps, gs = shifted(pa), shifted(ga)
+    assert pa.data_ptr() % 16 == 0 and ga.data_ptr() % 16 == 0 and ps.data_ptr() % 16 == 4 and gs.data_ptr() % 16 == 4
+    want = _bits_of_op(pa, ga)
+    for a, b in zip(want, _bits_of_op(pa, ga)):
+        assert torch.equal(a, b)
+    pp = ps.detach().requires_grad_(True)
+    assert pp.data_ptr() == ps.data_ptr()
+    loss, state = torch.ops.cerberus.inv_huber(pp, gs)
+    gr, = torch.autograd.grad(loss, pp)
+    for a, b in zip(want, (loss.detach(), state, gr)):
+        assert torch.equal(a, b)
+    assert bool(torch.isfinite(want[0])) and float(want[2].abs().max()) > 0

@@ -14,7 +14,18 @@ measured against its minuend mean(l^2).  Everywhere else it is held to its own f
 
 Shapes (B,H,W): the smallest at which each route can go wrong.  Scalar route (H*W odd or 2 mod 4, idle lanes): (1,1,1), (1,5,7),
 (2,37,53) (2 workgroups per image, a ragged last one), (1,3,66).  Vector route: (1,1,4), (2,8,64), (3,16,33) (odd W: a lane's 4
-pixels cross a row).  (2,128,256): 32 workgroups per image, so the per-image partial folds and the finish matter."""
+pixels cross a row).  (2,128,256): 32 workgroups per image, so the per-image partial folds matter; every thread of
+``metric_finish_kernel`` still reads at most ONE partial there, and no workgroup of ``seg_confusion_kernel`` takes a second chunk.
+
+Past one round (tests/reduction_cases.py, checked on the CPU by tests/test_reduction_tiers_cpu.py; the last section): (2,257,1024),
+vector, and (2,601,1023), scalar: 257 and 601 partials PER IMAGE, two images so that ``first = blockIdx.x * n`` matters, more than
+the 256 workgroups per image of ``seg_confusion`` (C = 3 there, C = 2 for ``warp_sad``).  At these sizes no seed keeps every ratio
+clear of the thresholds; the generator moves the few predictions that lie near one.  A sum over a whole map could hide one
+mis-addressed partial, so image 1 is also given ONE valid depth pixel, and ONE unmasked flow pixel, in the first chunk, in 255,
+256, 511, 512 and the last, and labels of one class only in the chunks that ``seg_confusion`` reaches by its stride.  The sums of
+image 1 then EQUAL that pixel's fp32 terms (as float64) where a term is made of correctly rounded operations only: |d|/g, d^2/g,
+d^2, the EPE and the mask.  The two depth sums that go through ``logf``, l^2 and |l|, are not held to equality, because the
+device's ``logf`` need not return numpy's last bit: they are held to float64 by ``check_bound`` at its floor (4 x 2^-23)."""
 import functools
 
 import numpy as np
@@ -24,7 +35,9 @@ import torch.nn.functional as F
 
 import cerberusnet_amd as ca
 import metrics_cases as cases
+import reduction_cases as rc
 from cerberusnet_amd.loss_functions.UnFlowLoss import mesh_grid, norm_grid
+from cerberusnet_amd.synth import hash_uniform
 from cerberusnet_amd.statistics import base as SB
 from cerberusnet_amd.statistics.depth import KEYS as DEPTH_KEYS
 
@@ -496,3 +509,111 @@ def test_the_device_part_of_add_sample_replays_in_a_graph(backend, monkeypatch):
             if key.startswith("Batch_") and key != "Batch_Loss":
                 assert len(data) == 2 and np.array_equal(data[0], data[1], equal_nan=True), key
                 assert np.isfinite(data[0]).any(), key
+
+
+# ---- past one round of the finish kernels: 257 and 601 partials per image, seg_confusion's stride ---------------------------------
+@functools.lru_cache(maxsize=None)
+def table_results(shape):
+    """The four ops on the whole maps of a table shape, computed once and shared; not written to."""
+    return all_ops(*(dev(a) for a in rc.metric_inputs(shape)))
+
+
+MARKERS = [(shape, k) for shape in rc.METRIC_CASES for k in rc.metric_marker_chunks(shape)]
+MARKER_IDS = ["%s-%d" % ("x".join(map(str, s)), k) for s, k in MARKERS]
+
+
+@pytest.mark.parametrize("shape", rc.METRIC_CASES)
+def test_table_shapes_confusion_matrix(shape):
+    x, t = rc.metric_inputs(shape)[:2]
+    want = cases.confusion_ref(x, t)
+    assert np.array_equal(host(table_results(shape)[0]), want) and (want > 0).all()
+    for backend in ("hip", "torch"):
+        assert np.array_equal(seg_class_results(x, t, backend=backend)[2], want.sum(axis=0)), backend
+
+
+@pytest.mark.parametrize("shape", rc.METRIC_CASES)
+def test_table_shapes_depth_statistics(shape):
+    p, g = rc.metric_inputs(shape)[2:4]
+    sums, counts = check_depth("depth %s" % (shape,), p, g)
+    assert torch.equal(sums, table_results(shape)[1]) and torch.equal(counts, table_results(shape)[2])
+
+
+@pytest.mark.parametrize("shape", rc.METRIC_CASES)
+def test_table_shapes_flow_statistics_and_sad(shape):
+    fp, fg, mask, img, seq = rc.metric_inputs(shape)[4:]
+    sums, counts, sad = check_flow("flow %s C=%d" % (shape, rc.METRIC_WARP_CHANNELS), fp, fg, mask, img, seq)
+    for a, b in zip((sums, counts, sad), table_results(shape)[3:]):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("shape,k", MARKERS, ids=MARKER_IDS)
+def test_one_valid_depth_pixel_in_chunk_k_of_image_1(shape, k):
+    """Image 1 (so that ``first = blockIdx.x * n`` is not 0) holds ONE valid pixel, inside chunk k: its counts are [1, ...] and
+    its sums are that pixel's terms, whichever thread of the finish kernel the chunk's partial falls to."""
+    p, g, pixel = rc.depth_metric_marker(shape, k)
+    sums, counts = ops.depth_metric_sums(dev(p), dev(g), cases.MIN_DEPTH, cases.MAX_DEPTH)
+    want_counts = cases.depth_counts32(p, g)
+    assert np.array_equal(host(counts), want_counts) and want_counts[1, 0] == 1
+    _, *terms32, _ = cases._depth_terms(p, g, np.float32)
+    _, *terms64, _ = cases._depth_terms(p, g, np.float64)
+    at = lambda term: float(term[1].reshape(-1)[pixel])
+    got = host(sums)[1]
+    # |d|/g, d^2/g and d^2 are a subtraction, a product and a division, each correctly rounded: the fp32 term, as float64
+    assert got[:3].tolist() == [at(t) for t in terms32[:3]], (got, [at(t) for t in terms32])
+    # l^2 and |l| go through logf: the bound of the module docstring with no stock error, i.e. its floor
+    ref = [at(t) for t in terms64[3:]]
+    check_bound("depth %s chunk %d log terms" % (shape, k), got[3:], ref, ref)
+    # image 0 keeps the bits of its full-map result
+    assert torch.equal(sums[0], table_results(shape)[1][0]) and torch.equal(counts[0], table_results(shape)[2][0])
+
+
+@pytest.mark.parametrize("shape,k", MARKERS, ids=MARKER_IDS)
+def test_one_unmasked_flow_pixel_in_chunk_k_of_image_1(shape, k):
+    fp, fg, mask, pixel = rc.flow_metric_marker(shape, k)
+    sums, counts = ops.flow_metric_sums(dev(fp), dev(fg), dev(mask))
+    assert host(counts)[1].tolist() == [1] and np.array_equal(host(counts), cases.flow_counts32(fp, fg, mask))
+    e32, _ = cases._flow_terms(fp, fg, mask, np.float32)
+    # two products, a sum and a square root, each correctly rounded: the fp32 term, as float64
+    assert host(sums)[1].tolist() == [float(e32[1].reshape(-1)[pixel]), 1.0], (host(sums)[1], e32[1].reshape(-1)[pixel])
+    assert torch.equal(sums[0], table_results(shape)[3][0]) and torch.equal(counts[0], table_results(shape)[4][0])
+
+
+@pytest.mark.parametrize("shape", rc.METRIC_CASES)
+def test_a_class_that_only_strided_chunks_of_image_1_hold(shape):
+    x, t, count = rc.confusion_marker(shape)
+    want = cases.confusion_ref(x, t)
+    got = host(ops.seg_confusion(dev(x), dev(t), 255))
+    assert np.array_equal(got[1, 2], want[1, 2]) and int(got[1, 2].sum()) == count > 0
+    assert int(got[0, 2].sum()) == 0 and np.array_equal(got, want)
+
+
+def test_a_table_shape_twice_and_misaligned_gives_the_same_bits():
+    shape = rc.case_of("metric", (2, 257, 1024))
+    arrays = [dev(a) for a in rc.metric_inputs(shape)]
+    assert all(a.data_ptr() % 16 == 0 for a in arrays)
+    want = table_results(shape)
+    for other in (all_ops(*arrays), all_ops(*(shifted(a) for a in arrays))):
+        for k, (a, b) in enumerate(zip(want, other)):
+            assert torch.equal(a, b), k
+
+
+def test_confusion_matrix_with_classes_switched_off():
+    """Logits of -inf: leading planes, a middle one, and every plane of a pixel (``torch.argmax`` then gives class 0)."""
+    shape, C = (2, 8, 64), 5
+    x, t = seg_inputs(shape, C, seed=6300)
+    pick = lambda seed: hash_uniform((2, 8, 64), seed, 0.0, 1.0) < 0.3
+    x[:, 0][pick(6301)] = -np.inf
+    x[:, 1][pick(6302)] = -np.inf
+    x[:, 3][pick(6303)] = -np.inf
+    x[:, :, 0, :4] = -np.inf
+    x[:, 1:, 1, :4] = -np.inf                        # only class 0 finite
+    x[:, :-1, 2, :4] = -np.inf                       # only the last class finite
+    t[:, :3, :4] = 2
+    pred = np.argmax(x, axis=1)
+    assert (pred[:, 0, :4] == 0).all() and (pred[:, 1, :4] == 0).all() and (pred[:, 2, :4] == C - 1).all()
+    assert torch.equal(torch.argmax(torch.from_numpy(x), dim=1), torch.from_numpy(pred))
+    assert (np.isneginf(x[:, 0]) & np.isneginf(x[:, 1])).sum() > 50
+    want = cases.confusion_ref(x, t)
+    for xin in (dev(x), shifted(dev(x))):            # both routes
+        assert np.array_equal(host(ops.seg_confusion(xin, dev(t), 255)), want)
+    assert want[0, 2, 0] >= 8 and want[0, 2, C - 1] >= 4

@@ -9,8 +9,15 @@ matter of luck (a CPU emulation of the fused order gave ratios up to 2.7 against
 
 Shapes: the smallest at which each route can go wrong.  Scalar route (H*W odd or 2 mod 4, one workgroup with idle lanes):
 (1,19,1,1), (1,2,5,7), (2,19,37,53), (1,19,3,66).  Vector route: (1,19,1,4), (2,19,8,64), (3,5,16,33) (odd W: a lane's 4
-pixels cross a row).  (2,150,9,20): many classes.  (2,19,128,256): 64 workgroups, so the partial fold and the final kernel
-matter.  (2,19,8,64) as a view 4 bytes into a larger buffer: misaligned pointers, bit-equal to the aligned call."""
+pixels cross a row).  (2,150,9,20): many classes.  (2,19,128,256): 64 workgroups, so the partial fold matters; every thread of
+``seg_ce_final_kernel`` still reads at most ONE partial there.  Its strided loop runs at the shapes of
+tests/reduction_cases.py (checked on the CPU by tests/test_reduction_tiers_cpu.py): (1,2,257,1024), vector, 257 partials -- thread
+0 adds two; (1,3,601,1023), scalar, 601 -- threads add three or two; (2,2,129,1028), vector, 260, the image boundary inside a
+chunk.  At those shapes a sum could hide one mis-addressed partial, so section 11 also counts ONE pixel, placed in the first
+chunk, in 255, 256, 511, 512 and in the last.  (2,19,8,64) as a view 4 bytes into a larger buffer: misaligned pointers, bit-equal
+to the aligned call; (2,2,129,1028) likewise.
+
+Section 12: logits of -inf (classes switched off), +inf, and finite logits up to 6e38 apart, on one shape per route."""
 import functools
 
 import numpy as np
@@ -19,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 import cerberusnet_amd as ca
+import reduction_cases as rc
 import seg_loss_cases as cases
 from cerberusnet_amd.synth import hash_uniform
 from conftest import l2_err, rel_err
@@ -39,6 +47,7 @@ IGNORES = [255, -1]
 COMBOS = [(shape, g, w, i) for shape in SHAPES for g, w, i in ((0.0, "ones", 255), (2.0, "dynamic", -1), (0.5, "given", 255))]
 COMBOS += [(shape, g, w, i) for shape in ((2, 19, 37, 53), (2, 19, 8, 64)) for g in GAMMAS for w in WEIGHTS for i in IGNORES
            if (shape, g, w, i) not in COMBOS]
+COMBOS += rc.SEG_CASES                    # past 256 partials: the strided loop of seg_ce_final_kernel (reduction_cases.py)
 
 
 def dev(a):
@@ -417,3 +426,164 @@ def test_wrapper_takes_the_stock_path_for_what_the_op_does_not_cover():
     wide = torch.zeros(shape[:3] + (shape[3] + 8,), device=DEV)
     wide[..., :shape[3]] = xd
     assert torch.equal(ca.seg_cross_entropy(wide[..., :shape[3]], td, w, ignore_index), fused)
+
+
+# ---- 11. past 256 partials: one counted pixel, placed where the finish kernel's loop wraps -------------------------------------
+@functools.lru_cache(maxsize=None)
+def _device_logits(shape):
+    """The logits of a table shape, host and device, shared by the marker cases; neither is written to."""
+    x = _inputs(shape, 255)[0]
+    return x, dev(x)
+
+
+def _bits(x, t, w, ignore_index, gamma):
+    xx = x.detach().requires_grad_(True)
+    assert xx.data_ptr() == x.data_ptr()
+    loss, lse, state = torch.ops.cerberus.seg_cross_entropy(xx, t, w, ignore_index, gamma)
+    g, = torch.autograd.grad(loss, xx)
+    return loss.detach(), lse, state, g
+
+
+MARKERS = [(c[0], k) for c in rc.SEG_CASES for k in rc.marker_chunks(rc.chunks(c[0][0] * c[0][2] * c[0][3], ca.ops.SEG_CHUNK_PIXELS))]
+
+
+@pytest.mark.parametrize("shape,k", MARKERS, ids=["%s-%d" % ("x".join(map(str, s)), k) for s, k in MARKERS])
+def test_one_counted_pixel_in_chunk_k(shape, k):
+    """Every label is the ignore value except one inside chunk k: the value is that pixel's cross-entropy (its weight cancels in
+    num / den), and the gradient is non-zero in that pixel's C entries and 0.0 everywhere else.  A partial that the finish
+    kernel skips or reads twice changes the value by all or twice of it."""
+    B, C, H, W = shape
+    x, xd = _device_logits(shape)
+    t, p, cls = rc.seg_marker(shape, k)
+    td, wd = dev(t), dev(rc.seg_marker_weights(C))
+    v, _, state, g = _bits(xd, td, wd, 255, 0.0)                              # one call: value, state and gradient
+    with torch.no_grad():
+        vs = _stock(xd, td, wd, 255, 0.0)
+    _check_value("seg %s one pixel in chunk %d" % (shape, k), v.item(), vs.item(), rc.seg_marker_ce64(x, p, cls))
+    b, r = divmod(p, H * W)
+    assert bool((g[b, :, r // W, r % W] != 0).all()) and int((g != 0).sum()) == C
+    assert float(state[1]) == float(rc.seg_marker_weights(C)[cls])               # den: the one weight, exactly
+
+
+def test_a_table_shape_twice_and_misaligned_gives_the_same_bits():
+    shape, gamma, kind, ignore_index = rc.case_of("seg", (2, 2, 129, 1028))
+    x, t = _inputs(shape, ignore_index)
+    xd, td, wd = dev(x), dev(t), dev(_weights(kind, shape, t, ignore_index))
+    buf = torch.zeros(xd.numel() + 1, device=DEV)
+    shifted = buf[1:].view(shape)
+    shifted.copy_(xd)
+    assert xd.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4 and shifted.is_contiguous()
+    want = _bits(xd, td, wd, ignore_index, gamma)
+    for other in (_bits(xd, td, wd, ignore_index, gamma), _bits(shifted, td, wd, ignore_index, gamma)):
+        for a, b in zip(want, other):
+            assert torch.equal(a, b)
+    assert bool(torch.isfinite(want[0])) and float(want[3].abs().max()) > 0
+
+
+# ---- 12. -inf, +inf and far-apart logits -------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _pattern_case(kind, shape, pattern):
+    return rc.inf_case(shape, pattern) if kind == "inf" else rc.far_case(shape, pattern)
+
+
+@functools.lru_cache(maxsize=None)
+def _pattern_reference(kind, shape, pattern, gamma):
+    """Value and logit gradient in float64 on the CPU, computed once per case."""
+    x, t, _, _ = _pattern_case(kind, shape, pattern)
+    x64 = torch.from_numpy(x).double().requires_grad_(True)
+    v = _stock(x64, torch.from_numpy(t), torch.from_numpy(rc.inf_weights(shape[1])).double(), rc.INF_IGNORE, gamma)
+    g, = torch.autograd.grad(v, x64)
+    return v.item(), g.numpy()
+
+
+def _check_pattern(kind, shape, pattern, gamma):
+    """Fused and stock fp32 on the GPU against float64 with the bounds of section 1; returns the fused gradient."""
+    x, t, mask, planes = _pattern_case(kind, shape, pattern)
+    ref_v, ref_g = _pattern_reference(kind, shape, pattern, gamma)
+    assert np.isfinite(ref_v) and np.isfinite(ref_g).all()
+    xd, td, wd = dev(x), dev(t), dev(rc.inf_weights(shape[1]))
+    v, g = _fused(xd, td, wd, rc.INF_IGNORE, gamma)
+    xs = xd.clone().requires_grad_(True)
+    vs = _stock(xs, td, wd, rc.INF_IGNORE, gamma)
+    gs, = torch.autograd.grad(vs, xs)
+    name = "seg %s %s gamma %g" % (shape, pattern, gamma)
+    _check_value(name, v.item(), vs.item(), ref_v)
+    _check_grad(name, g.cpu().numpy(), gs.cpu().numpy(), ref_g)
+    _, lse, _ = torch.ops.cerberus.seg_cross_entropy(xd, td, wd, rc.INF_IGNORE, gamma)
+    lse, lse64 = lse.cpu().numpy(), torch.logsumexp(torch.from_numpy(x).double(), 1).numpy()
+    for part in (mask, ~mask):                       # the changed pixels on their own: a plane at 3e38 would hide the others
+        assert rel_err(lse[part], lse64[part]) <= (shape[1] + 8) * 2.0 ** -24, (name, rel_err(lse[part], lse64[part]))
+    assert bool(torch.isfinite(g).all())
+    return g, mask, planes
+
+
+@pytest.mark.parametrize("shape", rc.INF_SHAPES)
+@pytest.mark.parametrize("gamma", [0.0, 2.0])
+@pytest.mark.parametrize("pattern", sorted(rc.INF_PATTERNS))
+def test_minus_inf_logits_against_float64(shape, gamma, pattern):
+    """Classes switched off by -inf on about a quarter of the pixels (never the target of a counted pixel): value, gradient and
+    lse as for finite logits, and a gradient of exactly 0.0 at every -inf logit."""
+    g, mask, planes = _check_pattern("inf", shape, pattern, gamma)
+    at_inf = g.movedim(1, 0)[planes][:, dev(mask)]
+    assert at_inf.numel() == len(planes) * int(mask.sum()) and bool((at_inf == 0).all())
+    if len(planes) < shape[1] - 1:                  # with one finite logit left, the target's, the softmax is exactly one-hot
+        assert float(g.movedim(1, 0)[:, dev(mask)].abs().max()) > 0
+
+
+@pytest.mark.parametrize("shape", rc.INF_SHAPES)
+@pytest.mark.parametrize("gamma", [0.0, 2.0])
+@pytest.mark.parametrize("pattern", sorted(rc.FAR_PATTERNS))
+def test_far_apart_finite_logits_against_float64(shape, gamma, pattern):
+    """Planes at +-1e4, at +-3e38 (x - m overflows to +-inf) and 104 and 88 below the maximum (exp underflows to 0 and to a
+    subnormal)."""
+    _check_pattern("far", shape, pattern, gamma)
+
+
+@pytest.mark.parametrize("shape", rc.INF_SHAPES)
+@pytest.mark.parametrize("pattern", sorted(rc.INF_PATTERNS))
+def test_minus_inf_logits_at_ignored_pixels_change_no_bit(shape, pattern):
+    x, t = _inputs(shape, rc.INF_IGNORE)
+    xi, ti, mask, _ = rc.inf_case(shape, pattern, ignored_only=True)
+    assert np.array_equal(t, ti) and mask.any() and np.isneginf(xi).any()
+    td, wd = dev(t), dev(rc.inf_weights(shape[1]))
+    clean, masked = _bits(dev(x), td, wd, rc.INF_IGNORE, 2.0), _bits(dev(xi), td, wd, rc.INF_IGNORE, 2.0)
+    for k in (0, 2, 3):                              # loss, state, gradient; lse is what it is at an ignored pixel
+        assert torch.equal(clean[k], masked[k]), k
+    assert torch.equal(clean[1][dev(~mask)], masked[1][dev(~mask)])
+
+
+@pytest.mark.parametrize("shape", rc.INF_SHAPES)
+@pytest.mark.parametrize("gamma", [0.0, 2.0])
+def test_a_counted_pixel_with_a_non_finite_loss_is_never_dropped(shape, gamma):
+    """DESIGN.md 3.18.  A target logit of -inf: +inf, as stock.  Every plane -inf: NaN, as stock.  A +inf plane: +inf if it is not
+    the target's and NaN if it is, where stock returns NaN both times."""
+    x, t = _inputs(shape, rc.INF_IGNORE)
+    C, hw = shape[1], shape[2] * shape[3]
+    wd, td = dev(rc.inf_weights(C)), dev(t)
+    flat = t.reshape(-1)
+    p = int(np.flatnonzero((flat != rc.INF_IGNORE) & (flat != 1) & (flat != 0))[7])        # counted, weight not 0
+    cls = int(flat[p])
+    other = 0 if cls != 0 else 2
+
+    def run(planes, value):
+        xn = x.copy()
+        for c in planes:
+            xn[p // hw, c].reshape(-1)[p % hw] = value
+        xd = dev(xn)
+        return ca.seg_cross_entropy(xd, td, wd, rc.INF_IGNORE, gamma), _stock(xd, td, wd, rc.INF_IGNORE, gamma)
+
+    def kind(v):
+        return "nan" if bool(torch.isnan(v)) else "+inf" if bool(torch.isposinf(v)) else "-inf" if bool(torch.isneginf(v)) else "finite"
+
+    v, vs = run([cls], -np.inf)                      # the target switched off: against the stock result of this very call
+    assert kind(v) == kind(vs) != "finite", (kind(v), kind(vs))
+    v, vs = run(range(C), -np.inf)
+    assert kind(v) == kind(vs) == "nan"
+    v, vs = run([other], np.inf)
+    assert kind(v) == "+inf" and kind(vs) == "nan"
+    v, vs = run([other, C - 1 if cls != C - 1 else C - 2], np.inf)
+    assert kind(v) == "+inf" and kind(vs) == "nan"
+    v, vs = run([cls], np.inf)
+    assert kind(v) == "nan" and kind(vs) == "nan"
+    clean, clean_s = run([], 0.0)
+    assert kind(clean) == kind(clean_s) == "finite"
