@@ -9,6 +9,7 @@ from .correlation_package.correlation import (Correlation, CorrelationFunction,
                                               CorrelationTorch)
 from .loss_functions.depth_losses import (BackprojectDepth, DepthAwareLoss, DepthReconstructionLossV1, InvHuberLoss,
                                           InvHuberLossPyr, Project3D, ScaleInvariantError, inv_huber_loss, reproject_warp)
+from .loss_functions.rmi import MultiScaleRMILoss, RMILoss, RMILossAux, rmi_loss
 from .loss_functions.seg_losses import FocalLoss2D, SegCrossEntropy, class_balance_weights, seg_cross_entropy
 from .loss_functions.UnFlowLoss import (TernaryLoss, area_pyramid, area_resize, census_loss, edge_smoothness, flow_warp,
                                          get_corresponding_map, get_occu_mask_backward, get_occu_mask_bidirection, mesh_grid,
@@ -20,4 +21,5 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "census_loss", "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "BackprojectDepth", "Project3D",
            "DepthReconstructionLossV1", "reproject_warp", "seg_cross_entropy", "class_balance_weights", "FocalLoss2D",
            "SegCrossEntropy", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
-           "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric", "ops"]
+           "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
+           "ops"]

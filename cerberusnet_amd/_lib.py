@@ -67,6 +67,9 @@ PROTOTYPES = {
     "cerberus_flow_metric_sums": (_I, [_P] * 6 + [_I64] + [_I] * 4 + [_P]),
     "cerberus_warp_sad_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_warp_sad": (_I, [_P] * 5 + [_I64] + [_I] * 5 + [_P]),
+    "cerberus_rmi_workspace_bytes": (_I64, [_I] * 5),
+    "cerberus_rmi_forward": (_I, [_P] * 11 + [_I64] + [_I] * 8 + [_P]),
+    "cerberus_rmi_backward": (_I, [_P] * 10 + [_I] * 8 + [_P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

@@ -1,7 +1,7 @@
 // api.hip -- the extern "C" surface declared in include/cerberus_hip.h.
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
-// census.hip, occlusion.hip, reproject.hip, seg_loss.hip, depth_loss.hip and metrics.hip.
+// census.hip, occlusion.hip, reproject.hip, seg_loss.hip, depth_loss.hip, metrics.hip and rmi_loss.hip.
 #include <atomic>
 #include <cstring>
 
@@ -592,6 +592,50 @@ int cerberus_warp_sad(const void *image, const void *source, const void *flow, v
     if (!image || !source || !flow || !sad) return CERB_EINVAL;
     if (metric_workspace_ok(workspace, workspace_bytes, warp_sad_workspace_bytes(B, H, W))) return CERB_EINVAL;
     return warp_sad(image, source, flow, sad, workspace, B, C, H, W, static_cast<hipStream_t>(stream));
+}
+
+// the RMI loss: logits (B,C,H,W) fp32, labels (B,H,W) int64.  The image is the launch grid's third dimension and the class
+// groups its second; a class is kept in 16 bits; one image's pixels are counted with an int.
+static int rmi_args_ok(int B, int C, int H, int W, int radius, int pool, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B < 0 || C < 1 || H <= 0 || W <= 0 || radius < 1 || pool < 1) return CERB_EINVAL;
+    if (radius != 3 || pool > rmi_max_pool()) return CERB_EUNSUPPORTED;      // the caller takes the stock ops there
+    if (static_cast<int64_t>(H) * W > 0x7fffffff - 1024 || B > 65535 || C > 32767) return CERB_ETOOLARGE;
+    int h, w;
+    if (!rmi_pooled_size(H, W, pool, &h, &w)) return CERB_EUNSUPPORTED;       // no 3 x 3 slice fits the pooled map
+    if (rmi_moment_workgroups(B, C, H, W, pool) > 0x7fffffff) return CERB_ETOOLARGE;
+    return CERB_OK;
+}
+
+int64_t cerberus_rmi_workspace_bytes(int B, int C, int H, int W, int pool) {
+    if (rmi_args_ok(B, C, H, W, 3, pool, CERB_F32) || B == 0) return 0;
+    return rmi_workspace_bytes(B, C, H, W, pool);
+}
+
+int cerberus_rmi_forward(const void *logits, const void *target, void *bce, void *state, void *la_map, void *pr_map, void *means,
+                         void *la_cov, void *pr_cov, void *la_pr_cov, void *workspace, int64_t workspace_bytes, int B, int C, int H,
+                         int W, int radius, int pool, int do_rmi, int dtype, void *stream) {
+    const int rc = rmi_args_ok(B, C, H, W, radius, pool, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !bce || !state || !workspace) return CERB_EINVAL;
+    if (do_rmi && (!la_map || !pr_map || !means || !la_cov || !pr_cov || !la_pr_cov)) return CERB_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(workspace) & 7) || workspace_bytes < rmi_workspace_bytes(B, C, H, W, pool)) return CERB_EINVAL;
+    return rmi_forward(logits, target, bce, state, la_map, pr_map, means, la_cov, pr_cov, la_pr_cov, workspace, B, C, H, W, pool,
+                       do_rmi != 0, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_rmi_backward(const void *logits, const void *target, const void *state, const void *la_map, const void *pr_map,
+                          const void *means, const void *grad_bce, const void *grad_pr_cov, const void *grad_la_pr_cov,
+                          void *grad_logits, int B, int C, int H, int W, int radius, int pool, int do_rmi, int dtype, void *stream) {
+    const int rc = rmi_args_ok(B, C, H, W, radius, pool, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !state || !grad_bce || !grad_logits) return CERB_EINVAL;
+    if (do_rmi && (!la_map || !pr_map || !means || !grad_pr_cov || !grad_la_pr_cov)) return CERB_EINVAL;
+    return rmi_backward(logits, target, state, la_map, pr_map, means, grad_bce, grad_pr_cov, grad_la_pr_cov, grad_logits, B, C, H, W,
+                        pool, do_rmi != 0, static_cast<hipStream_t>(stream));
 }
 
 static int smoothness_args_ok(int B, int Cf, int Ci, int H, int W, int degree, int dtype) {

@@ -280,6 +280,19 @@ int64_t warp_sad_workspace_bytes(int B, int H, int W);
 int warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace, int B, int C, int H, int W,
              hipStream_t s);
 
+// rmi_loss.hip: the region mutual information loss (radius 3, average pooling) up to its three (N,C,9,9) float64 covariance
+// matrices, and the backward from their gradients, fp32 logits (N,C,H,W), int64 labels (N,H,W); arguments are checked by api.hip.
+// `bce` / `grad_bce` point to ONE float in device memory, `state` to four; `workspace` is 8-byte aligned.
+int rmi_max_pool();
+bool rmi_pooled_size(int H, int W, int pool, int *h, int *w);     // false when a pooled side is shorter than the radius
+int64_t rmi_moment_workgroups(int B, int C, int H, int W, int pool);
+int64_t rmi_workspace_bytes(int B, int C, int H, int W, int pool);
+int rmi_forward(const void *logits, const void *target, void *bce, void *state, void *la_map, void *pr_map, void *means, void *la_cov,
+                void *pr_cov, void *la_pr_cov, void *workspace, int B, int C, int H, int W, int pool, int do_rmi, hipStream_t s);
+int rmi_backward(const void *logits, const void *target, const void *state, const void *la_map, const void *pr_map, const void *means,
+                 const void *grad_bce, const void *grad_pr_cov, const void *grad_la_pr_cov, void *grad_logits, int B, int C, int H,
+                 int W, int pool, int do_rmi, hipStream_t s);
+
 // corr_grad_prep.hip: dense gradOutput (LeakyReLU derivative applied from the stored volume's sign) from a
 // batch-strided one; `fwd` may be null (copy only)
 int corr_grad_prep(const void *gout, int64_t g_stride, const void *fwd, int64_t f_stride, void *dst, int B, int64_t count,

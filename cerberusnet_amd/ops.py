@@ -79,6 +79,10 @@ _def.define("seg_confusion(Tensor logits, Tensor target, int ignore_index) -> Te
 _def.define("depth_metric_sums(Tensor pred, Tensor gt, float min_depth, float max_depth) -> (Tensor sums, Tensor counts)")
 _def.define("flow_metric_sums(Tensor flow_pred, Tensor flow_gt, Tensor mask) -> (Tensor sums, Tensor counts)")
 _def.define("warp_sad(Tensor image, Tensor source, Tensor flow) -> Tensor")
+_def.define("rmi_moments(Tensor logits, Tensor target, int radius, int pool, bool do_rmi) -> (Tensor bce, Tensor la_cov, "
+            "Tensor pr_cov, Tensor la_pr_cov, Tensor la_map, Tensor pr_map, Tensor means, Tensor state)")
+_def.define("rmi_moments_backward(Tensor logits, Tensor target, Tensor la_map, Tensor pr_map, Tensor means, Tensor state, "
+            "Tensor grad_bce, Tensor grad_pr_cov, Tensor grad_la_pr_cov, int radius, int pool, bool do_rmi) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
 
@@ -955,6 +959,121 @@ def _seg_cross_entropy_backward_cuda(logits, target, weight, lse, state, grad_lo
     return grad
 
 
+# the RMI loss (rmi.py:33-207), csrc/rmi_loss.hip
+RMI_RADIUS = 3                          # the radius of the fused route
+RMI_MAX_POOL = 8                        # its largest pooling window (the labels of a window are staged in LDS)
+RMI_CELLS_PER_WORKGROUP = 256           # pooling windows per front-end workgroup
+RMI_CLASS_GROUP = 8                     # class planes per front-end workgroup
+RMI_POSITIONS_PER_WORKGROUP = 1024      # positions of the 3 x 3 slices per moment workgroup
+RMI_ENTRIES = 3 * 81                    # la_cov, pr_cov, la_pr_cov
+
+
+def _rmi_pooled(size, pool):
+    return (size + 2 * (pool // 2) - pool) // pool + 1
+
+
+def rmi_fused_shape_ok(C, H, W, radius, pool):
+    """The shapes cerberus::rmi_moments takes: radius 3, pool 1..8, a pooled map of at least 3 x 3 (the C ABI's own limits)."""
+    return (radius == RMI_RADIUS and 1 <= pool <= RMI_MAX_POOL and 1 <= C <= 32767 and H > 0 and W > 0
+            and H * W <= 0x7fffffff - 1024 and _rmi_pooled(H, pool) >= radius and _rmi_pooled(W, pool) >= radius)
+
+
+def _rmi_workspace_bytes(B, C, H, W, pool):
+    """cerberus_rmi_workspace_bytes in pure Python (a test holds the two equal): float64 -- a BCE and a count partial per
+    front-end workgroup (256 windows of 8 class planes of one image), 243 partial products per moment workgroup (1024 positions
+    of one (n, c))."""
+    if not (0 < B <= 65535 and pool >= 1 and rmi_fused_shape_ok(C, H, W, RMI_RADIUS, pool)):
+        return 0
+    pad = pool // 2
+    cells = ((H - 1 + pad) // pool + 1) * ((W - 1 + pad) // pool + 1)
+    parts = B * ((C + RMI_CLASS_GROUP - 1) // RMI_CLASS_GROUP) * ((cells + RMI_CELLS_PER_WORKGROUP - 1) // RMI_CELLS_PER_WORKGROUP)
+    positions = (_rmi_pooled(H, pool) - 2) * (_rmi_pooled(W, pool) - 2)
+    chunks = (positions + RMI_POSITIONS_PER_WORKGROUP - 1) // RMI_POSITIONS_PER_WORKGROUP
+    if B * C * chunks > 0x7fffffff:
+        return 0
+    return 8 * (2 * parts + B * C * chunks * RMI_ENTRIES)
+
+
+def _rmi_check(logits, target, radius, pool, what):
+    if logits.dim() != 4:
+        raise RuntimeError("%s: logits must be a 4-D (B,C,H,W) tensor, got %s" % (what, tuple(logits.shape)))
+    if logits.dtype != torch.float32:
+        raise RuntimeError("%s: logits must be float32, got %s (16-bit logits take the stock-op path of "
+                           "loss_functions.rmi_loss)" % (what, logits.dtype))
+    if target.dtype != torch.int64:
+        raise RuntimeError("%s: target must be int64, got %s" % (what, target.dtype))
+    if target.device != logits.device:
+        raise RuntimeError("%s: inputs on different devices: %s, %s" % (what, logits.device, target.device))
+    B, C, H, W = logits.shape
+    if tuple(target.shape) != (B, H, W):
+        raise RuntimeError("%s: target must be (B,H,W) = %s, got %s" % (what, (B, H, W), tuple(target.shape)))
+    if B == 0 or not rmi_fused_shape_ok(C, H, W, radius, pool):
+        raise RuntimeError("%s: needs radius 3, a pool of 1..8 and a pooled map of at least 3 x 3, got %s, radius %d, pool %d "
+                           "(loss_functions.rmi_loss takes the stock-op path)" % (what, tuple(logits.shape), radius, pool))
+
+
+def _rmi_shapes(B, C, H, W, pool, do_rmi):
+    if not do_rmi:
+        return (0,), (0,), (0,)
+    return (B, C, 9, 9), (B, C, _rmi_pooled(H, pool), _rmi_pooled(W, pool)), (B, C, 2, 9)
+
+
+def _rmi_moments_cuda(logits, target, radius, pool, do_rmi):
+    what = "cerberus::rmi_moments"
+    _rmi_check(logits, target, radius, pool, what)
+    x, t = logits.contiguous(), target.contiguous()
+    B, C, H, W = x.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_rmi_workspace_bytes(B, C, H, W, pool)
+    ws = torch.empty((max(ws_bytes, 8) + 7) // 8, dtype=torch.float64, device=x.device)
+    cov_shape, map_shape, mean_shape = _rmi_shapes(B, C, H, W, pool, do_rmi)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)
+    bce, state = f32(), f32(4)
+    la_cov, pr_cov, la_pr_cov, means = f64(*cov_shape), f64(*cov_shape), f64(*cov_shape), f64(*mean_shape)
+    la_map, pr_map = f32(*map_shape), f32(*map_shape)          # with do_rmi off: empty, and never written
+    ptr = lambda v: v.data_ptr() if do_rmi else None
+    with torch.cuda.device(x.device):
+        rc = lib.cerberus_rmi_forward(x.data_ptr(), t.data_ptr(), bce.data_ptr(), state.data_ptr(), ptr(la_map), ptr(pr_map),
+                                      ptr(means), ptr(la_cov), ptr(pr_cov), ptr(la_pr_cov), ws.data_ptr(), ws_bytes, B, C, H, W,
+                                      int(radius), int(pool), int(bool(do_rmi)), 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return bce, la_cov, pr_cov, la_pr_cov, la_map, pr_map, means, state
+
+
+def _rmi_moments_meta(logits, target, radius, pool, do_rmi):
+    B, C, H, W = logits.shape
+    cov_shape, map_shape, mean_shape = _rmi_shapes(B, C, H, W, pool, do_rmi)
+    f32 = lambda *shape: logits.new_empty(shape, dtype=torch.float32)
+    f64 = lambda *shape: logits.new_empty(shape, dtype=torch.float64)
+    return f32(), f64(*cov_shape), f64(*cov_shape), f64(*cov_shape), f32(*map_shape), f32(*map_shape), f64(*mean_shape), f32(4)
+
+
+def _rmi_moments_backward_cuda(logits, target, la_map, pr_map, means, state, grad_bce, grad_pr_cov, grad_la_pr_cov, radius, pool,
+                               do_rmi):
+    what = "cerberus::rmi_moments_backward"
+    _rmi_check(logits, target, radius, pool, what)
+    B, C, H, W = logits.shape
+    cov_shape, map_shape, mean_shape = _rmi_shapes(B, C, H, W, pool, do_rmi)
+    for v, name, shape, dtype in ((la_map, "la_map", map_shape, torch.float32), (pr_map, "pr_map", map_shape, torch.float32),
+                                  (means, "means", mean_shape, torch.float64), (state, "state", (4,), torch.float32),
+                                  (grad_pr_cov, "grad_pr_cov", cov_shape, torch.float64),
+                                  (grad_la_pr_cov, "grad_la_pr_cov", cov_shape, torch.float64)):
+        if v.dtype != dtype or v.device != logits.device or tuple(v.shape) != shape:
+            raise RuntimeError("%s: %s must be the %s %s tensor of the forward, got %s %s" % (what, name, dtype, shape, v.dtype,
+                                                                                           tuple(v.shape)))
+    x, t = logits.contiguous(), target.contiguous()
+    g = _grad_scalar(grad_bce, x, what)
+    grad = torch.empty_like(x)          # every element is written by the kernel
+    ptr = lambda v: v.contiguous().data_ptr() if do_rmi else None
+    with torch.cuda.device(x.device):
+        rc = _lib.get().cerberus_rmi_backward(x.data_ptr(), t.data_ptr(), state.contiguous().data_ptr(), ptr(la_map), ptr(pr_map),
+                                              ptr(means), g.data_ptr(), ptr(grad_pr_cov), ptr(grad_la_pr_cov), grad.data_ptr(), B, C,
+                                              H, W, int(radius), int(pool), int(bool(do_rmi)), 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return grad
+
+
 def _class_histogram_cuda(target, num_classes, ignore_index):
     what = "cerberus::class_histogram"
     if target.dtype != torch.int64:
@@ -1245,6 +1364,12 @@ _def.impl("seg_cross_entropy", _no_cpu("seg_cross_entropy"), "CPU")
 _def.impl("seg_cross_entropy_backward", _seg_cross_entropy_backward_cuda, "CUDA")
 _def.impl("seg_cross_entropy_backward", lambda x, t, w, lse, st, g, i: torch.empty_like(x), "Meta")
 _def.impl("seg_cross_entropy_backward", _no_cpu("seg_cross_entropy_backward"), "CPU")
+_def.impl("rmi_moments", _rmi_moments_cuda, "CUDA")
+_def.impl("rmi_moments", _rmi_moments_meta, "Meta")
+_def.impl("rmi_moments", _no_cpu("rmi_moments"), "CPU")
+_def.impl("rmi_moments_backward", _rmi_moments_backward_cuda, "CUDA")
+_def.impl("rmi_moments_backward", lambda x, *a: torch.empty_like(x), "Meta")
+_def.impl("rmi_moments_backward", _no_cpu("rmi_moments_backward"), "CPU")
 _def.impl("class_histogram", _class_histogram_cuda, "CUDA")
 _def.impl("class_histogram", lambda t, c, i: t.new_empty((c,), dtype=torch.int64), "Meta")
 _def.impl("class_histogram", _no_cpu("class_histogram"), "CPU")
@@ -1523,6 +1648,32 @@ def _seg_backward(ctx, grad_loss, _grad_lse, _grad_state):
     return gx, None, None, None, None
 
 
+def _rmi_setup(ctx, inputs, output):
+    logits, target, radius, pool, do_rmi = inputs
+    _bce, la_cov, _pr_cov, _la_pr_cov, la_map, pr_map, means, state = output
+    # the logits, and what the forward left: two pooled maps (1 / pool^2 of the logits each), 18 means per (n, c), the scalars
+    ctx.save_for_backward(logits, target, la_map, pr_map, means, state)
+    ctx.radius, ctx.pool, ctx.do_rmi = radius, pool, do_rmi
+    ctx.mark_non_differentiable(la_cov, la_map, pr_map, means, state)      # la_cov depends on the labels only
+
+
+def _rmi_backward(ctx, grad_bce, _g_la_cov, grad_pr_cov, grad_la_pr_cov, *_rest):
+    logits, target, la_map, pr_map, means, state = ctx.saved_tensors
+    if not ctx.needs_input_grad[0]:
+        return None, None, None, None, None
+    if grad_bce is None:
+        grad_bce = torch.zeros((), dtype=torch.float32, device=logits.device)
+    if ctx.do_rmi:
+        zeros = lambda: torch.zeros(logits.shape[:2] + (9, 9), dtype=torch.float64, device=logits.device)
+        grad_pr_cov = zeros() if grad_pr_cov is None else grad_pr_cov
+        grad_la_pr_cov = zeros() if grad_la_pr_cov is None else grad_la_pr_cov
+    else:
+        grad_pr_cov = grad_la_pr_cov = torch.empty((0,), dtype=torch.float64, device=logits.device)
+    gx = torch.ops.cerberus.rmi_moments_backward(logits, target, la_map, pr_map, means, state, grad_bce, grad_pr_cov, grad_la_pr_cov,
+                                                 ctx.radius, ctx.pool, ctx.do_rmi)
+    return gx, None, None, None, None
+
+
 def _inv_huber_setup(ctx, inputs, output):
     pred, gt = inputs
     _loss, state = output
@@ -1571,6 +1722,9 @@ torch.library.register_autograd("cerberus::edge_smoothness_backward", _no_double
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::seg_cross_entropy", _seg_backward, setup_context=_seg_setup)
 torch.library.register_autograd("cerberus::seg_cross_entropy_backward", _no_double_backward("seg_cross_entropy_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::rmi_moments", _rmi_backward, setup_context=_rmi_setup)
+torch.library.register_autograd("cerberus::rmi_moments_backward", _no_double_backward("rmi_moments_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::class_histogram", _histogram_backward, setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::inv_huber", _inv_huber_backward, setup_context=_inv_huber_setup)

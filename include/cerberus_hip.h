@@ -501,6 +501,43 @@ int64_t cerberus_warp_sad_workspace_bytes(int B, int H, int W);
 int cerberus_warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace,
                       int64_t workspace_bytes, int B, int C, int H, int W, int dtype, void *stream);
 
+/* The region mutual information loss (additions only: no ABI bump): the heavy part of RMILoss (rmi.py:33-207) for
+ * rmi_radius 3 and average pooling -- everything up to the three covariance matrices, and the backward from their gradients.
+ * The 9 x 9 algebra between the two (inverse, Cholesky, log) is the caller's.
+ *   logits : (B,C,H,W) fp32, C >= 1;  target : (B,H,W) int64;  pool = rmi_pool_size = rmi_pool_stride in 1..8 (1: no pooling)
+ *   valid = 0 <= target < C (a negative label is ignored like one >= C);  o_c = valid and target == c;  s = sigmoid(x)
+ *   bce[0] = sum_{valid pixels, all classes} (max(x,0) - x o + log1p(exp(-|x|))) / (n_valid + 1)
+ *   prob = valid ? s + 1e-6 : 1e-6;  la_map, pr_map : (B,C,h,w) fp32 = avg_pool2d(o / prob, pool, pool, pool / 2),
+ *          h = (H + 2 (pool / 2) - pool) / pool + 1 (the windows are disjoint and divide by pool^2 everywhere)
+ *   means  : (B,C,2,9) float64: the means of the 9 shifted (h-2) x (w-2) slices of la_map ([..,0,:]) and pr_map ([..,1,:])
+ *   la_cov, pr_cov, la_pr_cov : (B,C,9,9) float64 = L L^T, Pr Pr^T, L Pr^T of the slices minus their means
+ *   state  : 4 floats, overwritten: [bce, n_valid, 1 / (n_valid + 1), 0], read by the backward on the device
+ *   workspace : cerberus_rmi_workspace_bytes(B,C,H,W,pool) bytes (float64 partials; 0 for a size the calls reject), 8-byte
+ *          aligned, fully overwritten; no zero-fill needed
+ *   do_rmi == 0: only bce and state are written; the maps, means and matrices may be null.
+ * Forward: one pass over the logits (a lane owns one pooling window for 8 class planes; 8-byte loads when pool is 4 or 8, W is
+ * even, the logits are 8-byte and the labels 16-byte aligned; 4-byte loads otherwise -- both routes give the same bits), then the
+ * means and the centred products from the pooled maps in float64.  Every sum has a fixed order and no floating-point atomics:
+ * bit-reproducible for a given shape.
+ * Backward: grad_logits (B,C,H,W) = valid ? s (1 - s) g_pool / pool^2 + grad_bce[0] state[2] (s - o) : 0.0f, where g_pool is
+ * the gradient of the pooled probability gathered from grad_pr_cov = dloss/dpr_cov and grad_la_pr_cov = dloss/dla_pr_cov
+ * (float64 (B,C,9,9)); every element written exactly once (no zero-fill), one launch.  grad_bce points to ONE float in DEVICE
+ * memory (no host synchronisation: capturable).  la_cov carries no gradient (it depends on the labels only).
+ * Labels never form an address.  An ignored pixel is skipped by selection: a NaN logit there changes nothing.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, C < 1, H or W <= 0, radius or pool < 1
+ * CERB_EINVAL; radius != 3, pool > 8, a pooled side < 3 CERB_EUNSUPPORTED; H*W > 2^31 - 1025, B > 65535, C > 32767
+ * CERB_ETOOLARGE; then B == 0 returns 0 without a launch; a null pointer, a workspace that is misaligned or too small
+ * CERB_EINVAL -- all before any launch. */
+int64_t cerberus_rmi_workspace_bytes(int B, int C, int H, int W, int pool);
+int cerberus_rmi_forward(const void *logits, const void *target, void *bce, void *state, void *la_map, void *pr_map,
+                         void *means, void *la_cov, void *pr_cov, void *la_pr_cov, void *workspace,
+                         int64_t workspace_bytes, int B, int C, int H, int W, int radius, int pool, int do_rmi, int dtype,
+                         void *stream);
+int cerberus_rmi_backward(const void *logits, const void *target, const void *state, const void *la_map,
+                          const void *pr_map, const void *means, const void *grad_bce, const void *grad_pr_cov,
+                          const void *grad_la_pr_cov, void *grad_logits, int B, int C, int H, int W, int radius, int pool,
+                          int do_rmi, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
