@@ -14,7 +14,7 @@ from .loss_functions.seg_losses import FocalLoss2D, SegCrossEntropy, class_balan
 from .loss_functions.UnFlowLoss import (TernaryLoss, area_pyramid, area_resize, census_loss, edge_smoothness, flow_warp,
                                          get_corresponding_map, get_occu_mask_backward, get_occu_mask_bidirection, mesh_grid,
                                          norm_grid, photometric_loss)
-from .statistics import DepthMetric, MetricBase, OpticFlowMetric, SegmentationMetric
+from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
 
 __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp",
            "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness", "TernaryLoss",
@@ -22,4 +22,4 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "DepthReconstructionLossV1", "reproject_warp", "seg_cross_entropy", "class_balance_weights", "FocalLoss2D",
            "SegCrossEntropy", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
-           "ops"]
+           "PanopticMetric", "ops"]

@@ -67,6 +67,12 @@ PROTOTYPES = {
     "cerberus_flow_metric_sums": (_I, [_P] * 6 + [_I64] + [_I] * 4 + [_P]),
     "cerberus_warp_sad_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_warp_sad": (_I, [_P] * 5 + [_I64] + [_I] * 5 + [_P]),
+    "cerberus_center_peaks_max_kernel": (_I, []),
+    "cerberus_group_pixels_max_centers": (_I, []),
+    "cerberus_instance_overlap_max_bins": (_I, []),
+    "cerberus_center_peaks": (_I, [_P, _P] + [_I] * 3 + [ctypes.c_float, _I, _I, _P]),
+    "cerberus_group_pixels": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_uint64, _I, _P]),
+    "cerberus_instance_overlap": (_I, [_P] * 7 + [_I] * 5 + [_P]),
     "cerberus_rmi_workspace_bytes": (_I64, [_I] * 5),
     "cerberus_rmi_forward": (_I, [_P] * 11 + [_I64] + [_I] * 8 + [_P]),
     "cerberus_rmi_backward": (_I, [_P] * 10 + [_I] * 8 + [_P]),

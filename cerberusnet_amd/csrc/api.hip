@@ -594,6 +594,48 @@ int cerberus_warp_sad(const void *image, const void *source, const void *flow, v
     return warp_sad(image, source, flow, sad, workspace, B, C, H, W, static_cast<hipStream_t>(stream));
 }
 
+// the panoptic metric: fp32 heat map and offsets, int64 centres, counts, ids and classes.  The size limits are the metrics'
+// (an image's pixels are counted with an int, the image is a dimension of the launch grid).
+int cerberus_center_peaks_max_kernel(void) { return center_peaks_max_kernel(); }
+int cerberus_group_pixels_max_centers(void) { return group_pixels_max_centers(); }
+int cerberus_instance_overlap_max_bins(void) { return instance_overlap_max_bins(); }
+
+int cerberus_center_peaks(const void *heatmap, void *out, int B, int H, int W, float threshold, int nms_kernel, int dtype,
+                          void *stream) {
+    const int rc = metric_args_ok(B, 1, H, W, 1, dtype);
+    if (rc) return rc;
+    if (nms_kernel < 1 || nms_kernel % 2 == 0 || nms_kernel > center_peaks_max_kernel()) return CERB_EINVAL;
+    if (H > 65535 * 16) return CERB_ETOOLARGE;                              // 16-row tiles are the grid's second dimension
+    if (B == 0) return CERB_OK;
+    if (!heatmap || !out) return CERB_EINVAL;
+    return center_peaks(heatmap, out, B, H, W, threshold, nms_kernel, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_group_pixels(const void *offsets, const void *centers, const void *counts, const void *sem, void *out, int B, int H,
+                          int W, int max_centers, uint64_t thing_mask, int dtype, void *stream) {
+    const int rc = metric_args_ok(B, 2, H, W, 2, dtype);
+    if (rc) return rc;
+    if (max_centers < 1) return CERB_EINVAL;
+    if (max_centers > group_pixels_max_centers()) return CERB_EUNSUPPORTED;    // the caller takes the stock ops there
+    if (B == 0) return CERB_OK;
+    if (!offsets || !centers || !counts || !out) return CERB_EINVAL;           // sem may be null: every pixel is a thing
+    return group_pixels(offsets, centers, counts, sem, out, B, H, W, max_centers, thing_mask, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_instance_overlap(const void *pred_inst, const void *tgt_inst, const void *pred_seg, const void *tgt_seg, void *inter,
+                              void *pred_cls, void *tgt_cls, int B, int H, int W, int max_ids, int num_classes, void *stream) {
+    const int rc = metric_args_ok(B, 1, H, W, 1, CERB_F32);
+    if (rc) return rc;
+    if (max_ids < 1 || num_classes < 1) return CERB_EINVAL;
+    if (static_cast<int64_t>(max_ids) * (static_cast<int64_t>(max_ids) + 2 * static_cast<int64_t>(num_classes)) >
+        instance_overlap_max_bins())
+        return CERB_EUNSUPPORTED;                                            // a workgroup's bins live in LDS
+    if (B == 0) return CERB_OK;
+    if (!pred_inst || !tgt_inst || !pred_seg || !tgt_seg || !inter || !pred_cls || !tgt_cls) return CERB_EINVAL;
+    return instance_overlap(pred_inst, tgt_inst, pred_seg, tgt_seg, inter, pred_cls, tgt_cls, B, H, W, max_ids, num_classes,
+                            static_cast<hipStream_t>(stream));
+}
+
 // the RMI loss: logits (B,C,H,W) fp32, labels (B,H,W) int64.  The image is the launch grid's third dimension and the class
 // groups its second; a class is kept in 16 bits; one image's pixels are counted with an int.
 static int rmi_args_ok(int B, int C, int H, int W, int radius, int pool, int dtype) {

@@ -280,6 +280,18 @@ int64_t warp_sad_workspace_bytes(int B, int H, int W);
 int warp_sad(const void *image, const void *source, const void *flow, void *sad, void *workspace, int B, int C, int H, int W,
              hipStream_t s);
 
+// panoptic.hip: the device side of the panoptic metric, forward only; arguments are checked by api.hip.  heatmap / out: (B,H,W)
+// fp32; offsets: (B,2,H,W) fp32; centers: (B,kmax,2) int64; counts: (B,) int64; sem (may be null), the four maps and `out` of
+// group_pixels: (B,H,W) int64; inter (B,M,M), pred_cls / tgt_cls (B,M,C) int64, zeroed on the stream by the call.
+int center_peaks_max_kernel();
+int group_pixels_max_centers();
+int instance_overlap_max_bins();
+int center_peaks(const void *heatmap, void *out, int B, int H, int W, float threshold, int nms_kernel, hipStream_t s);
+int group_pixels(const void *offsets, const void *centers, const void *counts, const void *sem, void *out, int B, int H, int W,
+                 int kmax, uint64_t thing_mask, hipStream_t s);
+int instance_overlap(const void *pred_inst, const void *tgt_inst, const void *pred_seg, const void *tgt_seg, void *inter,
+                     void *pred_cls, void *tgt_cls, int B, int H, int W, int M, int C, hipStream_t s);
+
 // rmi_loss.hip: the region mutual information loss (radius 3, average pooling) up to its three (N,C,9,9) float64 covariance
 // matrices, and the backward from their gradients, fp32 logits (N,C,H,W), int64 labels (N,H,W); arguments are checked by api.hip.
 // `bce` / `grad_bce` point to ONE float in device memory, `state` to four; `workspace` is 8-byte aligned.

@@ -79,6 +79,10 @@ _def.define("seg_confusion(Tensor logits, Tensor target, int ignore_index) -> Te
 _def.define("depth_metric_sums(Tensor pred, Tensor gt, float min_depth, float max_depth) -> (Tensor sums, Tensor counts)")
 _def.define("flow_metric_sums(Tensor flow_pred, Tensor flow_gt, Tensor mask) -> (Tensor sums, Tensor counts)")
 _def.define("warp_sad(Tensor image, Tensor source, Tensor flow) -> Tensor")
+_def.define("center_peaks(Tensor heatmap, float threshold, int nms_kernel) -> Tensor")
+_def.define("group_pixels(Tensor offsets, Tensor centers, Tensor counts, Tensor? sem, int thing_mask) -> Tensor")
+_def.define("instance_overlap(Tensor pred_inst, Tensor tgt_inst, Tensor pred_seg, Tensor tgt_seg, int max_ids, int num_classes) -> "
+            "(Tensor inter, Tensor pred_cls, Tensor tgt_cls)")
 _def.define("rmi_moments(Tensor logits, Tensor target, int radius, int pool, bool do_rmi) -> (Tensor bce, Tensor la_cov, "
             "Tensor pr_cov, Tensor la_pr_cov, Tensor la_map, Tensor pr_map, Tensor means, Tensor state)")
 _def.define("rmi_moments_backward(Tensor logits, Tensor target, Tensor la_map, Tensor pr_map, Tensor means, Tensor state, "
@@ -1315,6 +1319,127 @@ def _flow_metric_sums_meta(flow_pred, flow_gt, mask):
     return flow_pred.new_empty((B, 2), dtype=torch.float64), flow_pred.new_empty((B, 1), dtype=torch.int64)
 
 
+# the panoptic metric (nnet_training/statistics/panoptic.py, utilities/panoptic_post_processing.py), csrc/panoptic.hip
+CENTER_PEAKS_MAX_KERNEL = 15            # odd NMS windows 1..15: the halo of a 16 x 64 LDS tile
+GROUP_PIXELS_MAX_CENTERS = 4096         # centres per image, walked through LDS 256 at a time; more: the stock chain
+INSTANCE_OVERLAP_MAX_BINS = 16128       # max_ids * (max_ids + 2 * num_classes) 32-bit LDS bins (63 KiB): 101 ids x 19 classes fit
+
+
+def thing_mask_of(thing_list):
+    """The 64-bit mask ``group_pixels`` takes: bit c set for every thing class c; None if a class lies outside [0, 64) (the
+    caller takes the stock ops then)."""
+    mask = 0
+    for c in thing_list:
+        c = int(c)
+        if not 0 <= c < 64:
+            return None
+        mask |= 1 << c
+    return mask
+
+
+def _heatmap_shape(heatmap, what):
+    if heatmap.dim() == 4 and heatmap.shape[1] == 1:
+        return (heatmap.shape[0],) + tuple(heatmap.shape[2:])
+    if heatmap.dim() == 3:
+        return tuple(heatmap.shape)
+    raise RuntimeError("%s: heatmap must be (B,1,H,W) or (B,H,W), got %s" % (what, tuple(heatmap.shape)))
+
+
+def _center_peaks_cuda(heatmap, threshold, nms_kernel):
+    what = "cerberus::center_peaks"
+    B, H, W = _heatmap_shape(heatmap, what)
+    _metric_check(what, [("heatmap", heatmap)], [tuple(heatmap.shape)])
+    if nms_kernel < 1 or nms_kernel % 2 == 0 or nms_kernel > CENTER_PEAKS_MAX_KERNEL:
+        raise RuntimeError("%s: nms_kernel must be odd and lie in 1..%d, got %d" % (what, CENTER_PEAKS_MAX_KERNEL, nms_kernel))
+    x = heatmap.contiguous()
+    out = torch.empty_like(x)               # every element is written by the kernel; the input never is
+    with torch.cuda.device(x.device):
+        rc = _lib.get().cerberus_center_peaks(x.data_ptr(), out.data_ptr(), B, H, W, ctypes.c_float(threshold), int(nms_kernel), 0,
+                                              _stream_ptr(x))
+    _lib.check(rc, what)
+    return out
+
+
+def _group_pixels_cuda(offsets, centers, counts, sem, thing_mask):
+    what = "cerberus::group_pixels"
+    if offsets.dim() != 4 or offsets.shape[1] != 2:
+        raise RuntimeError("%s: offsets must be a 4-D (B,2,H,W) tensor, got %s" % (what, tuple(offsets.shape)))
+    B, _, H, W = offsets.shape
+    if centers.dim() != 3 or centers.shape[0] != B or centers.shape[2] != 2:
+        raise RuntimeError("%s: centers must be (B,Kmax,2) with B = %d, got %s" % (what, B, tuple(centers.shape)))
+    kmax = centers.shape[1]
+    tensors = [("offsets", offsets), ("centers", centers), ("counts", counts)] + ([("sem", sem)] if sem is not None else [])
+    shapes = [(B, 2, H, W), (B, kmax, 2), (B,)] + ([(B, H, W)] if sem is not None else [])
+    _metric_check(what, tensors, shapes, {"centers": torch.int64, "counts": torch.int64, "sem": torch.int64})
+    if kmax > GROUP_PIXELS_MAX_CENTERS:
+        raise RuntimeError("%s: at most %d centres per image, got %d (utilities.panoptic_post_processing takes the stock-op path "
+                           "above it)" % (what, GROUP_PIXELS_MAX_CENTERS, kmax))
+    thing_mask = int(thing_mask) & 0xFFFFFFFFFFFFFFFF      # the schema's int is signed: bit 63 arrives as the sign
+    if kmax == 0:                          # no centre anywhere: nothing to launch
+        return torch.zeros((B, H, W), dtype=torch.int64, device=offsets.device)
+    off, ctr, cnt = offsets.contiguous(), centers.contiguous(), counts.contiguous()
+    sm = sem.contiguous() if sem is not None else None
+    out = torch.empty((B, H, W), dtype=torch.int64, device=off.device)
+    with torch.cuda.device(off.device):
+        rc = _lib.get().cerberus_group_pixels(off.data_ptr(), ctr.data_ptr(), cnt.data_ptr(), sm.data_ptr() if sm is not None else None,
+                                              out.data_ptr(), B, H, W, kmax, int(thing_mask), 0, _stream_ptr(off))
+    _lib.check(rc, what)
+    return out
+
+
+def _instance_overlap_cuda(pred_inst, tgt_inst, pred_seg, tgt_seg, max_ids, num_classes):
+    what = "cerberus::instance_overlap"
+    if pred_inst.dim() != 3:
+        raise RuntimeError("%s: pred_inst must be a 3-D (B,H,W) tensor, got %s" % (what, tuple(pred_inst.shape)))
+    B, H, W = pred_inst.shape
+    names = ("pred_inst", "tgt_inst", "pred_seg", "tgt_seg")
+    _metric_check(what, list(zip(names, (pred_inst, tgt_inst, pred_seg, tgt_seg))), [(B, H, W)] * 4, dict.fromkeys(names, torch.int64))
+    M, C = int(max_ids), int(num_classes)
+    if M < 1 or C < 1 or M * (M + 2 * C) > INSTANCE_OVERLAP_MAX_BINS:
+        raise RuntimeError("%s: max_ids and num_classes must be positive with max_ids * (max_ids + 2 * num_classes) <= %d, got %d "
+                           "and %d" % (what, INSTANCE_OVERLAP_MAX_BINS, M, C))
+    maps = [t.contiguous() for t in (pred_inst, tgt_inst, pred_seg, tgt_seg)]
+    dev = maps[0].device
+    inter = torch.empty((B, M, M), dtype=torch.int64, device=dev)               # zeroed on the stream by the call
+    pred_cls = torch.empty((B, M, C), dtype=torch.int64, device=dev)
+    tgt_cls = torch.empty((B, M, C), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.get().cerberus_instance_overlap(*[m.data_ptr() for m in maps], inter.data_ptr(), pred_cls.data_ptr(),
+                                                  tgt_cls.data_ptr(), B, H, W, M, C, _stream_ptr(maps[0]))
+    _lib.check(rc, what)
+    return inter, pred_cls, tgt_cls
+
+
+def _group_pixels_meta(offsets, centers, counts, sem, thing_mask):
+    return offsets.new_empty((offsets.shape[0],) + tuple(offsets.shape[2:]), dtype=torch.int64)
+
+
+def _instance_overlap_meta(pred_inst, tgt_inst, pred_seg, tgt_seg, max_ids, num_classes):
+    B = pred_inst.shape[0]
+    return (pred_inst.new_empty((B, max_ids, max_ids), dtype=torch.int64), pred_inst.new_empty((B, max_ids, num_classes), dtype=torch.int64),
+            pred_inst.new_empty((B, max_ids, num_classes), dtype=torch.int64))
+
+
+def center_peaks(heatmap, threshold=0.1, nms_kernel=3):
+    """``cerberus::center_peaks``: the thresholded, non-maximum-suppressed copy of a (B,1,H,W) or (B,H,W) float32 CUDA heat
+    map (-1 everywhere but at the peaks); the input is not written."""
+    return torch.ops.cerberus.center_peaks(heatmap, float(threshold), int(nms_kernel))
+
+
+def group_pixels(offsets, centers, counts, sem=None, thing_mask=0xFFFFFFFFFFFFFFFF):
+    """``cerberus::group_pixels``: the (B,H,W) int64 instance ids (1 + the index of the nearest centre) of (B,2,H,W) float32
+    CUDA offsets for (B,Kmax,2) int64 centres of which ``counts[b]`` are valid; with ``sem`` only pixels of a class whose bit
+    is set in ``thing_mask`` keep their id."""
+    mask = int(thing_mask)
+    return torch.ops.cerberus.group_pixels(offsets, centers, counts, sem, mask - (1 << 64) if mask >= 1 << 63 else mask)
+
+
+def instance_overlap(pred_inst, tgt_inst, pred_seg, tgt_seg, max_ids, num_classes):
+    """``cerberus::instance_overlap``: the (B,M,M) intersection counts of two (B,H,W) int64 CUDA id maps and the (B,M,C) class
+    histograms of each one's instances."""
+    return torch.ops.cerberus.instance_overlap(pred_inst, tgt_inst, pred_seg, tgt_seg, int(max_ids), int(num_classes))
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -1394,6 +1519,15 @@ _def.impl("flow_metric_sums", _no_cpu("flow_metric_sums"), "CPU")
 _def.impl("warp_sad", _warp_sad_cuda, "CUDA")
 _def.impl("warp_sad", lambda im, src, fl: im.new_empty((im.shape[0],), dtype=torch.float64), "Meta")
 _def.impl("warp_sad", _no_cpu("warp_sad"), "CPU")
+_def.impl("center_peaks", _center_peaks_cuda, "CUDA")
+_def.impl("center_peaks", lambda h, t, k: torch.empty_like(h), "Meta")
+_def.impl("center_peaks", _no_cpu("center_peaks"), "CPU")
+_def.impl("group_pixels", _group_pixels_cuda, "CUDA")
+_def.impl("group_pixels", _group_pixels_meta, "Meta")
+_def.impl("group_pixels", _no_cpu("group_pixels"), "CPU")
+_def.impl("instance_overlap", _instance_overlap_cuda, "CUDA")
+_def.impl("instance_overlap", _instance_overlap_meta, "Meta")
+_def.impl("instance_overlap", _no_cpu("instance_overlap"), "CPU")
 _def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
 _def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
 _def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
@@ -1730,5 +1864,5 @@ torch.library.register_autograd("cerberus::class_histogram", _histogram_backward
 torch.library.register_autograd("cerberus::inv_huber", _inv_huber_backward, setup_context=_inv_huber_setup)
 torch.library.register_autograd("cerberus::inv_huber_backward", _no_double_backward("inv_huber_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
-for _name in ("seg_confusion", "depth_metric_sums", "flow_metric_sums", "warp_sad"):
+for _name in ("seg_confusion", "depth_metric_sums", "flow_metric_sums", "warp_sad", "center_peaks", "group_pixels", "instance_overlap"):
     torch.library.register_autograd("cerberus::" + _name, _metric_backward(_name), setup_context=lambda ctx, inputs, output: None)

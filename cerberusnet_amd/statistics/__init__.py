@@ -5,6 +5,7 @@ the reference's operation order that makes the same single copy
 from .base import MetricBase
 from .depth import DepthMetric
 from .optical_flow import OpticFlowMetric
+from .panoptic import PanopticMetric
 from .semantic import SegmentationMetric
 
-__all__ = ["MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric"]
+__all__ = ["MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric", "PanopticMetric"]

@@ -538,6 +538,48 @@ int cerberus_rmi_backward(const void *logits, const void *target, const void *st
                           const void *grad_la_pr_cov, void *grad_logits, int B, int C, int H, int W, int radius, int pool,
                           int do_rmi, int dtype, void *stream);
 
+/* The device side of the panoptic metric (additions only: no ABI bump): what the reference's PanopticMetric
+ * (nnet_training/statistics/panoptic.py) and utilities/panoptic_post_processing.py do to the centre heat map, the offset map and
+ * the id / class maps of every image.  Forward only, no host synchronisation, no floating-point atomics: capturable and
+ * bit-reproducible.
+ *
+ * cerberus_center_peaks: heatmap (B,H,W) fp32 (a (B,1,H,W) map is the same memory) -> out (B,H,W) fp32, every element written.
+ *   v = x <= threshold ? -1 : x;  out = v where v equals the maximum of v over the nms_kernel x nms_kernel window clipped to the
+ *   image, else -1: the map that F.threshold(.., -1), max_pool2d(nms_kernel, 1, (nms_kernel-1)/2) and `hmp[hmp != pooled] = -1`
+ *   leave behind.  Compares only: exact.  As in that chain a NaN passes the threshold and is the maximum of every window that
+ *   holds it: the NaN pixel and every pixel within the window's reach of it give -1.  The input is not written.  nms_kernel is
+ *   odd and at most cerberus_center_peaks_max_kernel() (15).
+ *
+ * cerberus_group_pixels: offsets (B,2,H,W) fp32 in (dy, dx) order, centers (B,max_centers,2) int64 (y, x), counts (B,) int64
+ *   (the valid rows of each image; clamped to [0, max_centers]), sem (B,H,W) int64 or NULL -> out (B,H,W) int64 =
+ *   1 + argmin_k sqrtf(dy dy + dx dx), dy = float(cy_k) - (float(y) + off_y), dx = float(cx_k) - (float(x) + off_x), all fp32
+ *   without contraction; the first minimal index wins, a NaN distance counts as the minimum (torch.argmin's rule).  With sem,
+ *   the id is kept where 0 <= sem < 64 and bit sem of thing_mask is set, else 0.  An image with no centre gives zeros.  Centres
+ *   are walked through LDS in chunks of 256; max_centers is at most cerberus_group_pixels_max_centers() (4096).
+ *
+ * cerberus_instance_overlap: pred_inst, tgt_inst, pred_seg, tgt_seg (B,H,W) int64 -> inter (B,M,M), pred_cls (B,M,C), tgt_cls
+ *   (B,M,C) int64, M = max_ids, C = num_classes: inter[b,i,j] = the pixels of image b with predicted id i and target id j;
+ *   pred_cls[b,i,c] = those of predicted id i with predicted class c; tgt_cls[b,j,c] likewise for the target.  A pixel with
+ *   either id outside [0, M) is skipped in all three; a class outside [0, C) is skipped in its class histogram only.  The
+ *   outputs are zeroed on the stream by the call itself (a kernel) and added to with integer adds (32-bit LDS bins per
+ *   workgroup, one 64-bit global add per non-empty bin).  M (M + 2 C) is at most cerberus_instance_overlap_max_bins() (16128:
+ *   63 KiB of LDS; M = 101 with C = 19 fits).
+ *
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, a size <= 0, an even nms_kernel or one outside
+ * 1..15, max_centers, max_ids or num_classes < 1 CERB_EINVAL; H*W > 2^31 - 1025, B > 65535 or H > 16 * 65535 (center_peaks)
+ * CERB_ETOOLARGE; max_centers or the bin count above its limit CERB_EUNSUPPORTED; then B == 0 returns 0 without a launch; a null
+ * pointer (other than sem) CERB_EINVAL -- all before any launch. */
+int cerberus_center_peaks_max_kernel(void);
+int cerberus_group_pixels_max_centers(void);
+int cerberus_instance_overlap_max_bins(void);
+int cerberus_center_peaks(const void *heatmap, void *out, int B, int H, int W, float threshold, int nms_kernel, int dtype,
+                          void *stream);
+int cerberus_group_pixels(const void *offsets, const void *centers, const void *counts, const void *sem, void *out, int B,
+                          int H, int W, int max_centers, uint64_t thing_mask, int dtype, void *stream);
+int cerberus_instance_overlap(const void *pred_inst, const void *tgt_inst, const void *pred_seg, const void *tgt_seg,
+                              void *inter, void *pred_cls, void *tgt_cls, int B, int H, int W, int max_ids, int num_classes,
+                              void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
