@@ -9,6 +9,8 @@ from .correlation_package.correlation import (Correlation, CorrelationFunction,
                                               CorrelationTorch)
 from .loss_functions.depth_losses import (BackprojectDepth, DepthAwareLoss, DepthReconstructionLossV1, InvHuberLoss,
                                           InvHuberLossPyr, Project3D, ScaleInvariantError, inv_huber_loss, reproject_warp)
+from .loss_functions.ohem_losses import (MixSoftmaxCrossEntropyLoss, MixSoftmaxCrossEntropyOHEMLoss,
+                                         SoftmaxCrossEntropyOHEMLoss, seg_ohem_cross_entropy)
 from .loss_functions.rmi import MultiScaleRMILoss, RMILoss, RMILossAux, rmi_loss
 from .loss_functions.seg_losses import FocalLoss2D, SegCrossEntropy, class_balance_weights, seg_cross_entropy
 from .loss_functions.UnFlowLoss import (TernaryLoss, area_pyramid, area_resize, census_loss, edge_smoothness, flow_warp,
@@ -20,6 +22,7 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness", "TernaryLoss",
            "census_loss", "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "BackprojectDepth", "Project3D",
            "DepthReconstructionLossV1", "reproject_warp", "seg_cross_entropy", "class_balance_weights", "FocalLoss2D",
-           "SegCrossEntropy", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
+           "SegCrossEntropy", "seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss",
+           "MixSoftmaxCrossEntropyOHEMLoss", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
            "PanopticMetric", "ops"]

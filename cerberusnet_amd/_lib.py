@@ -57,6 +57,11 @@ PROTOTYPES = {
     "cerberus_seg_cross_entropy_forward": (_I, [_P] * 7 + [_I64] + [_I] * 4 + [_I64, ctypes.c_float, _I, _P]),
     "cerberus_seg_cross_entropy_backward": (_I, [_P] * 7 + [_I] * 4 + [_I64, _I, _P]),
     "cerberus_class_histogram": (_I, [_P, _P, _I64, _I, _I64, _P]),
+    "cerberus_seg_ohem_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_seg_ohem_forward": (_I, [_P] * 9 + [_I64] + [_I] * 4 + [_I64, ctypes.c_float, _I64, _I, _P]),
+    "cerberus_seg_ohem_backward": (_I, [_P] * 8 + [_I] * 4 + [_I64, _I, _P]),
+    "cerberus_seg_ohem_digit_bits": (_I, [_I]),
+    "cerberus_seg_ohem_bins": (_I, []),
     "cerberus_inv_huber_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_inv_huber_forward": (_I, [_P] * 5 + [_I64] + [_I] * 6 + [_P]),
     "cerberus_inv_huber_backward": (_I, [_P] * 5 + [_I] * 6 + [_P]),

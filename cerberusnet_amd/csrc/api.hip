@@ -486,6 +486,47 @@ int cerberus_class_histogram(const void *target, void *counts, int64_t count, in
     return class_histogram(target, counts, count, num_classes, ignore_index, static_cast<hipStream_t>(stream));
 }
 
+// OHEM cross-entropy: the tensors of the segmentation loss.  Pixels are counted with an int, as above.
+static int seg_ohem_args_ok(int B, int C, int H, int W, int dtype) {
+    const int rc = loss_dtype_ok(dtype);
+    if (rc) return rc;
+    if (B < 0 || C < 1 || H <= 0 || W <= 0) return CERB_EINVAL;
+    if (C < 2 || static_cast<int64_t>(B) * H * W > 0x7fffffff - 1024) return CERB_EUNSUPPORTED;
+    return CERB_OK;
+}
+
+int64_t cerberus_seg_ohem_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || static_cast<int64_t>(B) * H * W > 0x7fffffff - 1024) return 0;
+    return seg_ohem_workspace_bytes(B, H, W);
+}
+
+int cerberus_seg_ohem_forward(const void *logits, const void *target, const void *weight, void *loss, void *prob, void *lse,
+                              void *state, void *counts, void *workspace, int64_t workspace_bytes, int B, int C, int H, int W,
+                              int64_t ignore_index, float thresh, int64_t min_kept, int dtype, void *stream) {
+    const int rc = seg_ohem_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (thresh != thresh) return CERB_EINVAL;
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !weight || !loss || !prob || !lse || !state || !counts || !workspace) return CERB_EINVAL;
+    if (workspace_bytes < seg_ohem_workspace_bytes(B, H, W) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return CERB_EINVAL;
+    return seg_ohem_forward(logits, target, weight, loss, prob, lse, state, counts, workspace, B, C, H, W, ignore_index, thresh,
+                            min_kept, static_cast<hipStream_t>(stream));
+}
+
+int cerberus_seg_ohem_backward(const void *logits, const void *target, const void *weight, const void *prob, const void *lse,
+                               const void *state, const void *grad_loss, void *grad_logits, int B, int C, int H, int W,
+                               int64_t ignore_index, int dtype, void *stream) {
+    const int rc = seg_ohem_args_ok(B, C, H, W, dtype);
+    if (rc) return rc;
+    if (B == 0) return CERB_OK;
+    if (!logits || !target || !weight || !prob || !lse || !state || !grad_loss || !grad_logits) return CERB_EINVAL;
+    return seg_ohem_backward(logits, target, weight, prob, lse, state, grad_loss, grad_logits, B, C, H, W, ignore_index,
+                             static_cast<hipStream_t>(stream));
+}
+
+int cerberus_seg_ohem_digit_bits(int digit) { return seg_ohem_digit_bits(digit); }
+int cerberus_seg_ohem_bins(void) { return seg_ohem_bins(); }
+
 // the supervised depth loss: prediction (B,h,w), ground truth (B,H,W), fp32.  Pixels of the prediction are counted with an int
 // (a workgroup's last pixel index may run 1023 past the end before it is tested); offsets into the ground truth are 64-bit.
 static int inv_huber_args_ok(int B, int h, int w, int H, int W, int dtype) {

@@ -255,6 +255,18 @@ int seg_ce_backward(const void *logits, const void *target, const void *weight, 
 int class_histogram_max_classes();
 int class_histogram(const void *target, void *counts, int64_t count, int num_classes, int64_t ignore_index, hipStream_t s);
 
+// seg_ohem.hip: cross-entropy with online hard example mining (same tensors as seg_loss.hip); the min_kept-th smallest target
+// probability is selected on the device by a radix select.  `loss` / `grad_loss` point to ONE float in device memory, `state`
+// to eight, `counts` to two int64; `workspace` is 16-byte aligned; arguments are checked by api.hip.
+int64_t seg_ohem_workspace_bytes(int B, int H, int W);
+int seg_ohem_forward(const void *logits, const void *target, const void *weight, void *loss, void *prob, void *lse, void *state,
+                     void *counts, void *workspace, int B, int C, int H, int W, int64_t ignore_index, float thresh, int64_t min_kept,
+                     hipStream_t s);
+int seg_ohem_backward(const void *logits, const void *target, const void *weight, const void *prob, const void *lse, const void *state,
+                      const void *grad_loss, void *grad_logits, int B, int C, int H, int W, int64_t ignore_index, hipStream_t s);
+int seg_ohem_digit_bits(int digit);
+int seg_ohem_bins();
+
 // depth_loss.hip: the supervised depth loss InvHuberLoss (berHu) as a scalar op, fp32: prediction (B,h,w), ground truth (B,H,W)
 // with H % h == 0 and W % w == 0 (a pyramid level gathers gt[b, y H/h, x W/w]); arguments are checked by api.hip.  `loss` /
 // `grad_loss` point to ONE float in device memory, `state` to four; `workspace` is 16-byte aligned.

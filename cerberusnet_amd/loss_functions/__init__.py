@@ -1,5 +1,7 @@
 from .depth_losses import (BackprojectDepth, DepthAwareLoss, DepthReconstructionLossV1, InvHuberLoss, InvHuberLossPyr, Project3D,
                            ScaleInvariantError, inv_huber_loss, reproject_warp)
+from .ohem_losses import (MixSoftmaxCrossEntropyLoss, MixSoftmaxCrossEntropyOHEMLoss, SoftmaxCrossEntropyOHEMLoss,
+                          seg_ohem_cross_entropy)
 from .rmi import MultiScaleRMILoss, RMILoss, RMILossAux, rmi_loss
 from .seg_losses import FocalLoss2D, SegCrossEntropy, class_balance_weights, seg_cross_entropy
 from .UnFlowLoss import (TernaryLoss, census_loss, edge_smoothness, flow_warp, get_corresponding_map, get_occu_mask_backward,
@@ -9,5 +11,6 @@ __all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoo
            "get_corresponding_map", "get_occu_mask_backward", "get_occu_mask_bidirection", "unFlowLoss",
            "BackprojectDepth", "Project3D", "DepthReconstructionLossV1", "reproject_warp",
            "seg_cross_entropy", "class_balance_weights", "FocalLoss2D", "SegCrossEntropy",
+           "seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss", "MixSoftmaxCrossEntropyOHEMLoss",
            "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss"]

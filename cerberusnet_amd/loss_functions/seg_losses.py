@@ -166,3 +166,15 @@ class SegCrossEntropy(_SegLoss):
 
     def _finish(self, ce_loss):
         return self.weight * ce_loss
+
+
+# The rest of the reference's seg_losses.py lives in ohem_losses.py (which imports this module); the names are reachable
+# from here as well, where the reference keeps them.
+_OHEM_NAMES = ("seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss", "MixSoftmaxCrossEntropyOHEMLoss")
+
+
+def __getattr__(name):
+    if name in _OHEM_NAMES:
+        from . import ohem_losses
+        return getattr(ohem_losses, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -73,6 +73,10 @@ _def.define("seg_cross_entropy(Tensor logits, Tensor target, Tensor weight, int 
 _def.define("seg_cross_entropy_backward(Tensor logits, Tensor target, Tensor weight, Tensor lse, Tensor state, Tensor grad_loss, "
             "int ignore_index) -> Tensor")
 _def.define("class_histogram(Tensor target, int num_classes, int ignore_index) -> Tensor")
+_def.define("seg_ohem_cross_entropy(Tensor logits, Tensor target, Tensor weight, int ignore_index, float thresh, int min_kept) -> "
+            "(Tensor loss, Tensor prob, Tensor lse, Tensor state, Tensor counts)")
+_def.define("seg_ohem_cross_entropy_backward(Tensor logits, Tensor target, Tensor weight, Tensor prob, Tensor lse, Tensor state, "
+            "Tensor grad_loss, int ignore_index) -> Tensor")
 _def.define("inv_huber(Tensor pred, Tensor gt) -> (Tensor loss, Tensor state)")
 _def.define("inv_huber_backward(Tensor pred, Tensor gt, Tensor state, Tensor grad_loss) -> Tensor")
 _def.define("seg_confusion(Tensor logits, Tensor target, int ignore_index) -> Tensor")
@@ -963,6 +967,71 @@ def _seg_cross_entropy_backward_cuda(logits, target, weight, lse, state, grad_lo
     return grad
 
 
+# OHEM cross-entropy (seg_losses.py:40-119), csrc/seg_ohem.hip
+OHEM_DIGIT_BITS = (11, 11, 10)          # the radix select fixes the 32 bits of a probability in three digits, from the top
+OHEM_BINS = 2048                        # bins of one digit's histogram (LDS per workgroup, then global)
+OHEM_SELECT_WORDS = 8                   # the select state in the workspace: prefix, rank, num_valid, branch
+OHEM_STATE_FLOATS = 8                   # [ce, den, 1 / den, threshold, keep_all, rank left among the ties at kth, 0, 0]
+
+
+def _seg_ohem_workspace_bytes(B, H, W):
+    """cerberus_seg_ohem_workspace_bytes in pure Python (a test holds the two equal): lse - x_t per pixel (the pixels rounded
+    up to a multiple of 4), an fp32 num, an fp32 den and a uint32 kept partial per 1024 pixels, the bins of the three digits
+    and the select state."""
+    if B <= 0 or H <= 0 or W <= 0 or B * H * W > 0x7fffffff - 1024:
+        return 0
+    n = B * H * W
+    words = (n + 3) // 4 * 4 + 3 * ((n + SEG_CHUNK_PIXELS - 1) // SEG_CHUNK_PIXELS) + len(OHEM_DIGIT_BITS) * OHEM_BINS
+    return (words + OHEM_SELECT_WORDS) * 4
+
+
+def _seg_ohem_cuda(logits, target, weight, ignore_index, thresh, min_kept):
+    what = "cerberus::seg_ohem_cross_entropy"
+    _seg_check(logits, target, weight, what)
+    if thresh != thresh:
+        raise RuntimeError("%s: thresh is NaN" % what)
+    x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    B, C, H, W = x.shape
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_seg_ohem_workspace_bytes(B, H, W)
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    ws = f((max(ws_bytes, 4) + 3) // 4)
+    loss, prob, lse, state = f(), f(B, H, W), f(B, H, W), f(OHEM_STATE_FLOATS)
+    counts = torch.empty((2,), dtype=torch.int64, device=x.device)
+    min_kept = max(-1, min(int(min_kept), 2 ** 62))       # what the kernels compare with a count below 2^31
+    with torch.cuda.device(x.device):
+        rc = lib.cerberus_seg_ohem_forward(x.data_ptr(), t.data_ptr(), w.data_ptr(), loss.data_ptr(), prob.data_ptr(), lse.data_ptr(),
+                                           state.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws_bytes, B, C, H, W,
+                                           int(ignore_index), ctypes.c_float(thresh), min_kept, 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return loss, prob, lse, state, counts
+
+
+def _seg_ohem_meta(logits, target, weight, ignore_index, thresh, min_kept):
+    B, _, H, W = logits.shape
+    f = lambda *shape: logits.new_empty(shape, dtype=torch.float32)
+    return f(), f(B, H, W), f(B, H, W), f(OHEM_STATE_FLOATS), logits.new_empty((2,), dtype=torch.int64)
+
+
+def _seg_ohem_backward_cuda(logits, target, weight, prob, lse, state, grad_loss, ignore_index):
+    what = "cerberus::seg_ohem_cross_entropy_backward"
+    _seg_check(logits, target, weight, what)
+    B, C, H, W = logits.shape
+    for t, name, shape in ((prob, "prob", (B, H, W)), (lse, "lse", (B, H, W)), (state, "state", (OHEM_STATE_FLOATS,))):
+        if t.dtype != torch.float32 or t.device != logits.device or tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s must be the float32 %s tensor of the forward, got %s %s" % (what, name, shape, t.dtype,
+                                                                                                  tuple(t.shape)))
+    x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    g = _grad_scalar(grad_loss, x, what)
+    grad = torch.empty_like(x)          # every element is written by the kernel
+    with torch.cuda.device(x.device):
+        rc = _lib.get().cerberus_seg_ohem_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), prob.contiguous().data_ptr(),
+                                                   lse.contiguous().data_ptr(), state.contiguous().data_ptr(), g.data_ptr(),
+                                                   grad.data_ptr(), B, C, H, W, int(ignore_index), 0, _stream_ptr(x))
+    _lib.check(rc, what)
+    return grad
+
+
 # the RMI loss (rmi.py:33-207), csrc/rmi_loss.hip
 RMI_RADIUS = 3                          # the radius of the fused route
 RMI_MAX_POOL = 8                        # its largest pooling window (the labels of a window are staged in LDS)
@@ -1495,6 +1564,12 @@ _def.impl("rmi_moments", _no_cpu("rmi_moments"), "CPU")
 _def.impl("rmi_moments_backward", _rmi_moments_backward_cuda, "CUDA")
 _def.impl("rmi_moments_backward", lambda x, *a: torch.empty_like(x), "Meta")
 _def.impl("rmi_moments_backward", _no_cpu("rmi_moments_backward"), "CPU")
+_def.impl("seg_ohem_cross_entropy", _seg_ohem_cuda, "CUDA")
+_def.impl("seg_ohem_cross_entropy", _seg_ohem_meta, "Meta")
+_def.impl("seg_ohem_cross_entropy", _no_cpu("seg_ohem_cross_entropy"), "CPU")
+_def.impl("seg_ohem_cross_entropy_backward", _seg_ohem_backward_cuda, "CUDA")
+_def.impl("seg_ohem_cross_entropy_backward", lambda x, t, w, p, lse, st, g, i: torch.empty_like(x), "Meta")
+_def.impl("seg_ohem_cross_entropy_backward", _no_cpu("seg_ohem_cross_entropy_backward"), "CPU")
 _def.impl("class_histogram", _class_histogram_cuda, "CUDA")
 _def.impl("class_histogram", lambda t, c, i: t.new_empty((c,), dtype=torch.int64), "Meta")
 _def.impl("class_histogram", _no_cpu("class_histogram"), "CPU")
@@ -1782,6 +1857,26 @@ def _seg_backward(ctx, grad_loss, _grad_lse, _grad_state):
     return gx, None, None, None, None
 
 
+def _seg_ohem_setup(ctx, inputs, output):
+    logits, target, weight, ignore_index, _thresh, _min_kept = inputs
+    _loss, prob, lse, state, counts = output
+    # the logits, and what the forward left: prob and lse (8 B per pixel against 4 C), the threshold and 1 / den on the device
+    ctx.save_for_backward(logits, target, weight, prob, lse, state)
+    ctx.ignore_index = ignore_index
+    ctx.mark_non_differentiable(prob, lse, state, counts)
+
+
+def _seg_ohem_backward(ctx, grad_loss, *_grads):
+    logits, target, weight, prob, lse, state = ctx.saved_tensors
+    if ctx.needs_input_grad[2]:
+        raise RuntimeError("cerberus::seg_ohem_cross_entropy has no gradient for its class weights: "
+                           "loss_functions.seg_ohem_cross_entropy takes the stock-op path for a weight that requires grad")
+    gx = None
+    if ctx.needs_input_grad[0]:
+        gx = torch.ops.cerberus.seg_ohem_cross_entropy_backward(logits, target, weight, prob, lse, state, grad_loss, ctx.ignore_index)
+    return gx, None, None, None, None, None
+
+
 def _rmi_setup(ctx, inputs, output):
     logits, target, radius, pool, do_rmi = inputs
     _bce, la_cov, _pr_cov, _la_pr_cov, la_map, pr_map, means, state = output
@@ -1856,6 +1951,9 @@ torch.library.register_autograd("cerberus::edge_smoothness_backward", _no_double
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::seg_cross_entropy", _seg_backward, setup_context=_seg_setup)
 torch.library.register_autograd("cerberus::seg_cross_entropy_backward", _no_double_backward("seg_cross_entropy_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::seg_ohem_cross_entropy", _seg_ohem_backward, setup_context=_seg_ohem_setup)
+torch.library.register_autograd("cerberus::seg_ohem_cross_entropy_backward", _no_double_backward("seg_ohem_cross_entropy_backward"),
                                 setup_context=lambda ctx, inputs, output: None)
 torch.library.register_autograd("cerberus::rmi_moments", _rmi_backward, setup_context=_rmi_setup)
 torch.library.register_autograd("cerberus::rmi_moments_backward", _no_double_backward("rmi_moments_backward"),

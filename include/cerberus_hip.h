@@ -421,6 +421,44 @@ int cerberus_seg_cross_entropy_backward(const void *logits, const void *target, 
 int cerberus_class_histogram(const void *target, void *counts, int64_t count, int num_classes,
                              int64_t ignore_index, void *stream);
 
+/* Cross-entropy with online hard example mining (OHEM) as one differentiable scalar (additions only: no ABI bump):
+ * SoftmaxCrossEntropyOHEMLoss (seg_losses.py:40-95) with the selection on the device.  Tensors as for
+ * cerberus_seg_cross_entropy_*; thresh is compared in fp32; min_kept is any integer.
+ *   valid(p) = target(p) != ignore_index && 0 <= target(p) < C;  prob(p) = exp(x_t(p) - lse(p))
+ *   num_valid = #valid.  min_kept >= num_valid: every valid pixel is kept (a NaN prob too), threshold = +inf.  Else
+ *   min_kept > 0: kth = the min_kept-th smallest prob of the valid pixels (a NaN orders above every number), threshold =
+ *   kth > thresh ? kth : thresh, and thresh for a NaN kth.  Else threshold = thresh.
+ *   kept(p) = valid(p) && prob(p) <= threshold (every pixel tied at kth is kept)
+ *   loss[0] = sum_kept w[t] (lse - x_t) / sum_kept w[t]  (0 / 0 = NaN when nothing is kept)
+ *   prob   : (B,H,W) fp32, overwritten: -1 where the pixel is not valid;   lse : (B,H,W) fp32, overwritten (every pixel)
+ *   state  : 8 floats, overwritten: [ce, den, 1 / den, threshold, keep_all (1 or 0), the rank left among the pixels tied at
+ *            kth (exact below 2^24), 0, 0], read by the backward on the device
+ *   counts : 2 int64, overwritten: [num_valid, num_kept]
+ *   workspace : cerberus_seg_ohem_workspace_bytes(B,H,W) bytes, 16-byte aligned (lse - x_t per pixel, three partials per 1024
+ *            pixels, 3 x 2048 bins, 8 words of select state; 0 for a non-positive or too large size); the call zeroes what it
+ *            adds to with a kernel of its own (capturable)
+ * kth is exact: a radix select over the bits of prob, 11 / 11 / 10 bits from the top (cerberus_seg_ohem_digit_bits(0..2),
+ * cerberus_seg_ohem_bins() bins per digit).  Counts are integer adds, floating-point sums go through per-workgroup partials in
+ * a fixed order: the same bits on every run, on both routes (16-byte vector loads when H*W % 4 == 0 and the pointers are
+ * aligned; scalar otherwise) and in a replayed graph.  The forward reads the logits once; nothing is read on the host.
+ * A label outside [0, C) that is not ignore_index never forms an address and takes no part in the selection: it adds NaN to
+ * the numerator, as in cerberus_seg_cross_entropy_forward, and its gradient is zeros.
+ * Backward: grad_logits = grad_loss[0] * state[2] * w[t] * (softmax - onehot) at kept pixels (re-derived from prob and
+ * state[3], state[4]), exactly 0.0f elsewhere; every element is written once.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, C < 1, H or W <= 0 CERB_EINVAL; C < 2 or
+ * B*H*W > 2^31 - 1025 CERB_EUNSUPPORTED; a NaN thresh CERB_EINVAL; then B == 0 returns 0 without a launch; a null pointer, a
+ * workspace that is too small or misaligned CERB_EINVAL -- all before any launch. */
+int64_t cerberus_seg_ohem_workspace_bytes(int B, int H, int W);
+int cerberus_seg_ohem_forward(const void *logits, const void *target, const void *weight, void *loss, void *prob,
+                              void *lse, void *state, void *counts, void *workspace, int64_t workspace_bytes, int B,
+                              int C, int H, int W, int64_t ignore_index, float thresh, int64_t min_kept, int dtype,
+                              void *stream);
+int cerberus_seg_ohem_backward(const void *logits, const void *target, const void *weight, const void *prob,
+                               const void *lse, const void *state, const void *grad_loss, void *grad_logits, int B,
+                               int C, int H, int W, int64_t ignore_index, int dtype, void *stream);
+int cerberus_seg_ohem_digit_bits(int digit);
+int cerberus_seg_ohem_bins(void);
+
 /* The supervised depth loss InvHuberLoss (berHu) as one differentiable scalar (additions only: no ABI bump): the reference's
  * InvHuberLoss.forward (depth_losses.py:64-88) without `weight`, fp32.
  *   pred : (B,h,w) (a (B,1,h,w) prediction is the same memory);  gt : (B,H,W) with H % h == 0 and W % w == 0.  Pixel (y, x) of
