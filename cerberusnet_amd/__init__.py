@@ -11,12 +11,14 @@ from .loss_functions.depth_losses import (BackprojectDepth, DepthAwareLoss, Dept
                                           InvHuberLossPyr, Project3D, ScaleInvariantError, inv_huber_loss, reproject_warp)
 from .loss_functions.ohem_losses import (MixSoftmaxCrossEntropyLoss, MixSoftmaxCrossEntropyOHEMLoss,
                                          SoftmaxCrossEntropyOHEMLoss, seg_ohem_cross_entropy)
+from .loss_functions.panoptic_loss import DeeplabPanopticLoss, deeplab_panoptic_loss
 from .loss_functions.rmi import MultiScaleRMILoss, RMILoss, RMILossAux, rmi_loss
 from .loss_functions.seg_losses import FocalLoss2D, SegCrossEntropy, class_balance_weights, seg_cross_entropy
 from .loss_functions.UnFlowLoss import (TernaryLoss, area_pyramid, area_resize, census_loss, edge_smoothness, flow_warp,
                                          get_corresponding_map, get_occu_mask_backward, get_occu_mask_bidirection, mesh_grid,
                                          norm_grid, photometric_loss)
 from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
+from .utilities.panoptic_targets import PanopticTargetGenerator, panoptic_targets
 
 __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp",
            "mesh_grid", "norm_grid", "area_resize", "area_pyramid", "photometric_loss", "edge_smoothness", "TernaryLoss",
@@ -25,4 +27,4 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "SegCrossEntropy", "seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss",
            "MixSoftmaxCrossEntropyOHEMLoss", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
-           "PanopticMetric", "ops"]
+           "PanopticMetric", "deeplab_panoptic_loss", "DeeplabPanopticLoss", "panoptic_targets", "PanopticTargetGenerator", "ops"]

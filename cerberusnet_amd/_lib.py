@@ -78,6 +78,12 @@ PROTOTYPES = {
     "cerberus_center_peaks": (_I, [_P, _P] + [_I] * 3 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_group_pixels": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_uint64, _I, _P]),
     "cerberus_instance_overlap": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "cerberus_panoptic_targets_max_segments": (_I, []),
+    "cerberus_panoptic_targets_workspace_bytes": (_I64, [_I] * 4),
+    "cerberus_panoptic_targets": (_I, [_P, _I] + [_P] * 14 + [_I64] + [_I] * 5 + [_I64, _I, _I64, ctypes.c_float, _I, _P]),
+    "cerberus_panoptic_loss_workspace_bytes": (_I64, [_I] * 3),
+    "cerberus_panoptic_loss_forward": (_I, [_P] * 9 + [_I64] + [_I] * 3 + [ctypes.c_float, ctypes.c_float, _I, _I, _P]),
+    "cerberus_panoptic_loss_backward": (_I, [_P] * 10 + [_I] * 5 + [_P]),
     "cerberus_rmi_workspace_bytes": (_I64, [_I] * 5),
     "cerberus_rmi_forward": (_I, [_P] * 11 + [_I64] + [_I] * 8 + [_P]),
     "cerberus_rmi_backward": (_I, [_P] * 10 + [_I] * 8 + [_P]),

@@ -2,6 +2,7 @@
 // Argument validation + dispatch only; kernels live in corr_d4.hip / corr_d4_bwd.hip / corr_strip.hip / corr_coarse.hip /
 // corr_mfma.hip / corr_generic.hip, corr_grad_prep.hip, warp.hip, warp16.hip, warp_corr.hip, upsample.hip, photometric.hip,
 // census.hip, occlusion.hip, reproject.hip, seg_loss.hip, depth_loss.hip, metrics.hip and rmi_loss.hip.
+// (panoptic_train.hip carries the entry points of its own ops.)
 #include <atomic>
 #include <cstring>
 

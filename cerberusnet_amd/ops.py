@@ -93,6 +93,15 @@ _def.define("rmi_moments_backward(Tensor logits, Tensor target, Tensor la_map, T
             "Tensor grad_bce, Tensor grad_pr_cov, Tensor grad_la_pr_cov, int radius, int pool, bool do_rmi) -> Tensor")
 _def.define("edge_smoothness(Tensor flow, Tensor image, float alpha, int degree) -> Tensor")
 _def.define("edge_smoothness_backward(Tensor flow, Tensor image, Tensor grad_loss, float alpha, int degree) -> Tensor")
+_def.define("panoptic_targets(Tensor ids, Tensor seg_ids, Tensor seg_category, Tensor seg_flags, Tensor seg_count, Tensor gauss, "
+            "int ignore_label, int sigma, bool ignore_stuff_in_offset, int small_instance_area, float small_instance_weight, "
+            "bool ignore_crowd_in_semantic) -> (Tensor semantic, Tensor foreground, Tensor center, Tensor offset, "
+            "Tensor semantic_mask, Tensor center_mask, Tensor offset_mask, Tensor center_points)")
+_def.define("panoptic_loss(Tensor center_pred, Tensor center_tgt, Tensor? center_mask, Tensor offset_pred, Tensor offset_tgt, "
+            "Tensor? offset_mask, float center_weight, float offset_weight, int mode) -> (Tensor loss, Tensor state)")
+_def.define("panoptic_loss_backward(Tensor center_pred, Tensor center_tgt, Tensor? center_mask, Tensor offset_pred, "
+            "Tensor offset_tgt, Tensor? offset_mask, Tensor state, Tensor grad_loss, int mode) -> "
+            "(Tensor grad_center, Tensor grad_offset)")
 
 
 def _stream_ptr(t: torch.Tensor):
@@ -1509,6 +1518,161 @@ def instance_overlap(pred_inst, tgt_inst, pred_seg, tgt_seg, max_ids, num_classe
     return torch.ops.cerberus.instance_overlap(pred_inst, tgt_inst, pred_seg, tgt_seg, int(max_ids), int(num_classes))
 
 
+# the training side of the panoptic branch (datasets/cityscapes_panoptic_transform.py, loss_functions/panoptic_loss.py),
+# csrc/panoptic_train.hip
+PANOPTIC_TARGETS_MAX_SEGMENTS = 256     # rows of an image's segment table: one per thread of a workgroup; more: the stock route
+PANOPTIC_CHUNK_PIXELS = 1024            # pixels (elements) per workgroup: three fp32 partials each in the loss
+PANOPTIC_LOSS_MODES = {"reference": 0, "pixel": 1}
+_PANOPTIC_TARGET_NAMES = ("semantic", "foreground", "center", "offset", "semantic_mask", "center_mask", "offset_mask", "center_points")
+
+
+def _panoptic_targets_workspace_bytes(B, H, W, S):
+    """cerberus_panoptic_targets_workspace_bytes in pure Python (a test holds the two equal): per row three 64-bit moments, an
+    int64 category, two int32 centre coordinates and an int32 flag word; a 32-bit row per pixel, padded to 16 bytes."""
+    if B <= 0 or B > METRIC_MAX_BATCH or H <= 0 or W <= 0 or S <= 0 or S > PANOPTIC_TARGETS_MAX_SEGMENTS or H * W > 0x7fffffff - 1024:
+        return 0
+    return B * S * (24 + 8 + 8 + 4) + (B * H * W * 4 + 15) // 16 * 16
+
+
+def _panoptic_loss_workspace_bytes(B, H, W):
+    """cerberus_panoptic_loss_workspace_bytes in pure Python: an fp32 partial of sum f, sum m f and sum m per 1024 elements of
+    the centre term (B*H*W elements) and of the offset term (2*B*H*W)."""
+    if B <= 0 or H <= 0 or W <= 0 or 2 * B * H * W > 0x7fffffff - 1024:
+        return 0
+    n = B * H * W
+    return 3 * ((n + PANOPTIC_CHUNK_PIXELS - 1) // PANOPTIC_CHUNK_PIXELS + (2 * n + PANOPTIC_CHUNK_PIXELS - 1) // PANOPTIC_CHUNK_PIXELS) * 4
+
+
+def _panoptic_targets_check(ids, seg_ids, seg_category, seg_flags, seg_count, gauss, sigma, what):
+    if ids.dim() != 3 or ids.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("%s: ids must be a (B,H,W) int32 or int64 tensor, got %s %s" % (what, tuple(ids.shape), ids.dtype))
+    B, H, W = ids.shape
+    if seg_ids.dim() != 2 or seg_ids.shape[0] != B:
+        raise RuntimeError("%s: seg_ids must be (B,S) with B = %d, got %s" % (what, B, tuple(seg_ids.shape)))
+    S = seg_ids.shape[1]
+    size = 6 * int(sigma) + 3
+    for name, t, shape, dtype in (("seg_ids", seg_ids, (B, S), torch.int64), ("seg_category", seg_category, (B, S), torch.int64),
+                                  ("seg_flags", seg_flags, (B, S), torch.int32), ("seg_count", seg_count, (B,), torch.int64),
+                                  ("gauss", gauss, (size, size), torch.float32)):
+        if t.dtype != dtype or tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s must be %s %s, got %s %s" % (what, name, str(dtype).replace("torch.", ""), shape, t.dtype,
+                                                                    tuple(t.shape)))
+        if t.device != ids.device:
+            raise RuntimeError("%s: inputs on different devices: %s, %s" % (what, ids.device, t.device))
+    if sigma < 1:
+        raise RuntimeError("%s: sigma must be a positive integer, got %d" % (what, sigma))
+    if ids.numel() == 0 or S == 0:
+        raise RuntimeError("%s: needs at least one pixel and one table row, got ids %s and S = %d" % (what, tuple(ids.shape), S))
+    if S > PANOPTIC_TARGETS_MAX_SEGMENTS:
+        raise RuntimeError("%s: at most %d table rows per image, got %d (utilities.panoptic_targets takes the stock-op route "
+                           "above it)" % (what, PANOPTIC_TARGETS_MAX_SEGMENTS, S))
+    if B > METRIC_MAX_BATCH or H * W > 0x7fffffff - 1024:
+        raise RuntimeError("%s: %d images of %d pixels do not fit the kernels' launch grid" % (what, B, H * W))
+    return B, H, W, S
+
+
+def _panoptic_targets_empty(ids, S):
+    B, H, W = ids.shape
+    new = lambda shape, dtype: ids.new_empty(shape, dtype=dtype)
+    return (new((B, H, W), torch.int64), new((B, H, W), torch.int64), new((B, 1, H, W), torch.float32), new((B, 2, H, W), torch.float32),
+            new((B, H, W), torch.float32), new((B, H, W), torch.float32), new((B, H, W), torch.float32), new((B, S, 2), torch.float64))
+
+
+def _panoptic_targets_cuda(ids, seg_ids, seg_category, seg_flags, seg_count, gauss, ignore_label, sigma, ignore_stuff_in_offset,
+                           small_instance_area, small_instance_weight, ignore_crowd_in_semantic):
+    what = "cerberus::panoptic_targets"
+    B, H, W, S = _panoptic_targets_check(ids, seg_ids, seg_category, seg_flags, seg_count, gauss, sigma, what)
+    x = ids.contiguous()
+    tables = [t.contiguous() for t in (seg_ids, seg_category, seg_flags, seg_count, gauss)]
+    outs = _panoptic_targets_empty(x, S)            # every element is written by the kernels
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_panoptic_targets_workspace_bytes(B, H, W, S)
+    ws = torch.empty((max(ws_bytes, 16) + 7) // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.cerberus_panoptic_targets(x.data_ptr(), 1 if x.dtype == torch.int64 else 0, *[t.data_ptr() for t in tables],
+                                           *[o.data_ptr() for o in outs], ws.data_ptr(), ws_bytes, B, H, W, S, int(sigma),
+                                           int(ignore_label), int(bool(ignore_stuff_in_offset)), int(small_instance_area),
+                                           ctypes.c_float(small_instance_weight), int(bool(ignore_crowd_in_semantic)), _stream_ptr(x))
+    _lib.check(rc, what)
+    return outs
+
+
+def _panoptic_targets_meta(ids, seg_ids, seg_category, seg_flags, seg_count, gauss, ignore_label, sigma, ignore_stuff_in_offset,
+                           small_instance_area, small_instance_weight, ignore_crowd_in_semantic):
+    return _panoptic_targets_empty(ids, seg_ids.shape[1])
+
+
+def _panoptic_loss_check(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, mode, what):
+    if center_pred.dim() != 4 or center_pred.shape[1] != 1:
+        raise RuntimeError("%s: center_pred must be a 4-D (B,1,H,W) tensor, got %s" % (what, tuple(center_pred.shape)))
+    B, _, H, W = center_pred.shape
+    for name, t, shape in (("center_pred", center_pred, (B, 1, H, W)), ("center_tgt", center_tgt, (B, 1, H, W)),
+                           ("center_mask", center_mask, (B, H, W)), ("offset_pred", offset_pred, (B, 2, H, W)),
+                           ("offset_tgt", offset_tgt, (B, 2, H, W)), ("offset_mask", offset_mask, (B, H, W))):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: %s must be float32, got %s (16-bit and 64-bit tensors take the stock-op chain of "
+                               "loss_functions.deeplab_panoptic_loss)" % (what, name, t.dtype))
+        if t.device != center_pred.device:
+            raise RuntimeError("%s: inputs on different devices: %s, %s" % (what, center_pred.device, t.device))
+        if tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s must be %s, got %s" % (what, name, shape, tuple(t.shape)))
+    if mode not in (0, 1):
+        raise RuntimeError("%s: mode must be 0 (reference) or 1 (pixel), got %d" % (what, mode))
+    if center_pred.numel() == 0:
+        raise RuntimeError("%s: needs at least one pixel, got %s" % (what, tuple(center_pred.shape)))
+    if 2 * B * H * W > 0x7fffffff - 1024:
+        raise RuntimeError("%s: %d elements do not fit the kernels' 32-bit element index" % (what, 2 * B * H * W))
+    return B, H, W
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _panoptic_loss_cuda(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, center_weight, offset_weight, mode):
+    what = "cerberus::panoptic_loss"
+    B, H, W = _panoptic_loss_check(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, mode, what)
+    ts = [t.contiguous() if t is not None else None for t in (center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask)]
+    dev = ts[0].device
+    lib = _lib.get()
+    ws_bytes = lib.cerberus_panoptic_loss_workspace_bytes(B, H, W)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    state = torch.empty((2,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.cerberus_panoptic_loss_forward(*[_ptr(t) for t in ts], loss.data_ptr(), state.data_ptr(), ws.data_ptr(), ws_bytes, B, H, W,
+                                                ctypes.c_float(center_weight), ctypes.c_float(offset_weight), int(mode), 0,
+                                                _stream_ptr(ts[0]))
+    _lib.check(rc, what)
+    return loss, state
+
+
+def _panoptic_loss_meta(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, center_weight, offset_weight, mode):
+    return center_pred.new_empty((), dtype=torch.float32), center_pred.new_empty((2,), dtype=torch.float32)
+
+
+def _panoptic_loss_backward_cuda(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, state, grad_loss, mode):
+    what = "cerberus::panoptic_loss_backward"
+    B, H, W = _panoptic_loss_check(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, mode, what)
+    if state.dtype != torch.float32 or state.device != center_pred.device or tuple(state.shape) != (2,):
+        raise RuntimeError("%s: state must be the float32 (2,) tensor of the forward, got %s %s" % (what, state.dtype,
+                                                                                                   tuple(state.shape)))
+    ts = [t.contiguous() if t is not None else None for t in (center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask)]
+    gl = _grad_scalar(grad_loss, ts[0], what)
+    gc, go = torch.empty_like(ts[0]), torch.empty_like(ts[3])       # every element is written by the kernel
+    with torch.cuda.device(ts[0].device):
+        rc = _lib.get().cerberus_panoptic_loss_backward(*[_ptr(t) for t in ts], state.contiguous().data_ptr(), gl.data_ptr(),
+                                                        gc.data_ptr(), go.data_ptr(), B, H, W, int(mode), 0, _stream_ptr(ts[0]))
+    _lib.check(rc, what)
+    return gc, go
+
+
+def _panoptic_loss_backward_meta(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, state, grad_loss, mode):
+    return torch.empty_like(center_pred), torch.empty_like(offset_pred)
+
+
 def _no_cpu(name):
     def _raise(*_a, **_k):
         raise RuntimeError("cerberus::%s has no CPU implementation: this build is the "
@@ -1603,6 +1767,15 @@ _def.impl("group_pixels", _no_cpu("group_pixels"), "CPU")
 _def.impl("instance_overlap", _instance_overlap_cuda, "CUDA")
 _def.impl("instance_overlap", _instance_overlap_meta, "Meta")
 _def.impl("instance_overlap", _no_cpu("instance_overlap"), "CPU")
+_def.impl("panoptic_targets", _panoptic_targets_cuda, "CUDA")
+_def.impl("panoptic_targets", _panoptic_targets_meta, "Meta")
+_def.impl("panoptic_targets", _no_cpu("panoptic_targets"), "CPU")
+_def.impl("panoptic_loss", _panoptic_loss_cuda, "CUDA")
+_def.impl("panoptic_loss", _panoptic_loss_meta, "Meta")
+_def.impl("panoptic_loss", _no_cpu("panoptic_loss"), "CPU")
+_def.impl("panoptic_loss_backward", _panoptic_loss_backward_cuda, "CUDA")
+_def.impl("panoptic_loss_backward", _panoptic_loss_backward_meta, "Meta")
+_def.impl("panoptic_loss_backward", _no_cpu("panoptic_loss_backward"), "CPU")
 _def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
 _def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
 _def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
@@ -1920,6 +2093,27 @@ def _inv_huber_backward(ctx, grad_loss, _grad_state):
     return gp, None
 
 
+def _panoptic_loss_setup(ctx, inputs, output):
+    center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, _cw, _ow, mode = inputs
+    _loss, state = output
+    ctx.mode = mode
+    # the inputs and the two scales the forward left on the device: the backward recomputes every element's difference
+    ctx.save_for_backward(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, state)
+    ctx.mark_non_differentiable(state)
+
+
+def _panoptic_loss_backward(ctx, grad_loss, _grad_state):
+    center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, state = ctx.saved_tensors
+    if any(ctx.needs_input_grad[i] for i in (1, 2, 4, 5)):
+        raise RuntimeError("cerberus::panoptic_loss has no gradient for a target or a mask: loss_functions.deeplab_panoptic_loss "
+                           "takes the stock-op chain for targets that require grad")
+    gc = go = None
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[3]:
+        gc, go = torch.ops.cerberus.panoptic_loss_backward(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask,
+                                                           state, grad_loss, ctx.mode)
+    return (gc if ctx.needs_input_grad[0] else None, None, None, go if ctx.needs_input_grad[3] else None, None, None, None, None, None)
+
+
 def _histogram_backward(ctx, grad):
     raise RuntimeError("cerberus::class_histogram is not differentiable: it counts integer labels")
 
@@ -1964,3 +2158,13 @@ torch.library.register_autograd("cerberus::inv_huber_backward", _no_double_backw
                                 setup_context=lambda ctx, inputs, output: None)
 for _name in ("seg_confusion", "depth_metric_sums", "flow_metric_sums", "warp_sad", "center_peaks", "group_pixels", "instance_overlap"):
     torch.library.register_autograd("cerberus::" + _name, _metric_backward(_name), setup_context=lambda ctx, inputs, output: None)
+torch.library.register_autograd("cerberus::panoptic_loss", _panoptic_loss_backward, setup_context=_panoptic_loss_setup)
+torch.library.register_autograd("cerberus::panoptic_loss_backward", _no_double_backward("panoptic_loss_backward"),
+                                setup_context=lambda ctx, inputs, output: None)
+
+
+def _targets_backward(ctx, *grads):
+    raise RuntimeError("cerberus::panoptic_targets is not differentiable: it makes training targets from integer labels")
+
+
+torch.library.register_autograd("cerberus::panoptic_targets", _targets_backward, setup_context=lambda ctx, inputs, output: None)

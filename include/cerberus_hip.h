@@ -618,6 +618,74 @@ int cerberus_instance_overlap(const void *pred_inst, const void *tgt_inst, const
                               void *inter, void *pred_cls, void *tgt_cls, int B, int H, int W, int max_ids, int num_classes,
                               void *stream);
 
+/* The training side of the panoptic branch (additions only: no ABI bump): the Panoptic-DeepLab targets of the reference's
+ * PanopticTargetGenerator (datasets/cityscapes_panoptic_transform.py) from an id map on the device, and the centre / offset
+ * regression loss of its DeeplabPanopticLoss (loss_functions/panoptic_loss.py) as one differentiable scalar.  No host
+ * synchronisation, no floating-point atomics: capturable and bit-reproducible.  A workgroup owns 1024 consecutive pixels
+ * (elements); 16-byte loads and stores when H*W % 4 == 0 and the pointers are 16-byte aligned, 4-byte ones otherwise -- both
+ * routes give the same bits.
+ *
+ * cerberus_panoptic_targets: ids (B,H,W) int32 (ids_int64 == 0) or int64 (1), the decoded panoptic id map; seg_ids, seg_category
+ *   (B,S) int64; seg_flags (B,S) int32, bit 0 "thing", bit 1 "iscrowd"; seg_count (B,) int64, the live rows of each image's
+ *   table (clamped to [0,S]; rows past it are ignored whatever they hold); gauss ((6 sigma + 3)^2) fp32, the caller's table of
+ *   exp(-((x - x0)^2 + (y - y0)^2) / (2 sigma^2)), x0 = y0 = 3 sigma + 1.  S is at most
+ *   cerberus_panoptic_targets_max_segments() (256).  Ids among an image's live rows must be distinct: the result is otherwise
+ *   unspecified.  A pixel's row is the live row whose id it holds, if any.
+ *   Per live row: n, sum y, sum x over its pixels as 64-bit INTEGERS (any order, the same sums); cy = double(sum y) / double(n),
+ *   cx likewise; it has a centre if it is a thing and n > 0, and is small if it has a centre and n < small_instance_area.
+ *   center_points : (B,S,2) float64 (cy, cx), NaN for a row without a centre
+ *   semantic      : (B,H,W) int64: the row's category; ignore_label without a row, or for a crowd row if ignore_crowd_in_semantic
+ *   foreground    : (B,H,W) int64: 1 on things
+ *   center        : (B,H,W) fp32: max over the image's centres (Y,X) = ((int)cy, (int)cx) with 0 <= y - (Y - 3 sigma - 1) <
+ *                   6 sigma + 3 and likewise in x of gauss[y - (Y - 3 sigma - 1)][x - (X - 3 sigma - 1)], else 0
+ *   offset        : (B,2,H,W) fp32: float(cy - double(y)), float(cx - double(x)) on things, else 0
+ *   semantic_mask : (B,H,W) fp32: small_instance_weight on small things, else 1
+ *   center_mask   : (B,H,W) fp32: 1 on a row that is not crowd
+ *   offset_mask   : (B,H,W) fp32: 1 on a row that is not crowd and, if ignore_stuff_in_offset, is a thing
+ *   workspace : cerberus_panoptic_targets_workspace_bytes(B,H,W,S) bytes (the moments, a 32-bit row map, the rows' attributes; 0
+ *               for a size the call rejects), 16-byte aligned; the call zeroes what it adds to (a kernel).
+ *   Every output element is written exactly once.  Launches: zero, moments, finish (one workgroup per image), fill.
+ *   Errors: B < 0, a size <= 0, S <= 0, sigma < 1, ids_int64 not 0 / 1 CERB_EINVAL; S > 256 CERB_EUNSUPPORTED; H*W > 2^31 - 1025,
+ *   B > 65535 or sigma > 4096 CERB_ETOOLARGE; then B == 0 returns 0 without a launch; a null pointer, a workspace that is
+ *   misaligned or too small CERB_EINVAL -- all before any launch.
+ *
+ * cerberus_panoptic_loss_forward: center_pred, center_tgt (B,1,H,W), offset_pred, offset_tgt (B,2,H,W), center_mask, offset_mask
+ *   (B,H,W) or NULL, all fp32; masks are weights (any float), shared by the planes of their term.  With d = pred - tgt,
+ *   f = d d (centre) or |d| (offset), N the term's elements, and sums over the term's ELEMENTS (the offset mask counts twice):
+ *   mode 0 (reference): term = weight * sum f / N if the mask is NULL or sum m > 0, else 0 (the reference's `mean * mask` summed
+ *                       and divided by the mask's sum, with its gate evaluated on the device)
+ *   mode 1 (pixel)    : term = weight * sum_{m != 0} m f / sum m if sum m > 0, else 0; without a mask as mode 0.  An element
+ *                       with m == 0 is skipped by selection: a NaN there changes nothing.
+ *   loss[0] = centre term + offset term;  state : 2 floats, overwritten: the scales weight / N or weight / sum m (0 when a term
+ *   is gated off), read by the backward on the device.  In mode 0 a NaN anywhere gives NaN.
+ *   workspace : cerberus_panoptic_loss_workspace_bytes(B,H,W) bytes (three partials per 1024 elements of each term; 0 for a size
+ *               the calls reject), 16-byte aligned; no zero-fill needed.
+ *   Launches: one pass per term, then one workgroup that adds the partials in a fixed order.
+ * cerberus_panoptic_loss_backward: grad_center (B,1,H,W), grad_offset (B,2,H,W), every element written exactly once by ONE
+ *   launch: grad_loss[0] * scale * (2 d or sign(d), sign(0) = 0), times m in mode 1 with a mask; exactly 0.0f where m == 0 in
+ *   mode 1 and everywhere when the term's scale is 0.  grad_loss points to ONE float in DEVICE memory.
+ *   Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B < 0, a size <= 0, a mode other than 0 / 1
+ *   CERB_EINVAL; 2*B*H*W > 2^31 - 1025 CERB_ETOOLARGE; then B == 0 returns 0 without a launch; a null pointer (other than a
+ *   mask), a workspace that is misaligned or too small CERB_EINVAL -- all before any launch. */
+int cerberus_panoptic_targets_max_segments(void);
+int64_t cerberus_panoptic_targets_workspace_bytes(int B, int H, int W, int S);
+int cerberus_panoptic_targets(const void *ids, int ids_int64, const void *seg_ids, const void *seg_category,
+                              const void *seg_flags, const void *seg_count, const void *gauss, void *semantic,
+                              void *foreground, void *center, void *offset, void *semantic_mask, void *center_mask,
+                              void *offset_mask, void *center_points, void *workspace, int64_t workspace_bytes, int B, int H,
+                              int W, int S, int sigma, int64_t ignore_label, int ignore_stuff_in_offset,
+                              int64_t small_instance_area, float small_instance_weight, int ignore_crowd_in_semantic,
+                              void *stream);
+int64_t cerberus_panoptic_loss_workspace_bytes(int B, int H, int W);
+int cerberus_panoptic_loss_forward(const void *center_pred, const void *center_tgt, const void *center_mask,
+                                   const void *offset_pred, const void *offset_tgt, const void *offset_mask, void *loss,
+                                   void *state, void *workspace, int64_t workspace_bytes, int B, int H, int W,
+                                   float center_weight, float offset_weight, int mode, int dtype, void *stream);
+int cerberus_panoptic_loss_backward(const void *center_pred, const void *center_tgt, const void *center_mask,
+                                    const void *offset_pred, const void *offset_tgt, const void *offset_mask,
+                                    const void *state, const void *grad_loss, void *grad_center, void *grad_offset, int B,
+                                    int H, int W, int mode, int dtype, void *stream);
+
 /* Diagnostics / tuning knobs (process-wide, read at launch time, default 0):
  *   "corr_force_generic" : 1 = always use the generic kernels (testing)
  *   "corr_fwd_variant"   : 0 = auto, 1..8 = force one register-staged forward variant,
