@@ -116,6 +116,14 @@ def _dtype_code(t: torch.Tensor, what: str) -> int:
                            % (what, t.dtype)) from None
 
 
+def _fresh_like(t: torch.Tensor, dtype=None) -> torch.Tensor:
+    """An output "like ``t``" under the contract of every op here: ``t``'s shape, its dtype or ``dtype``, in a
+    fresh allocation with the default (NCHW) strides and storage offset 0 -- whatever ``t``'s own strides are.  Both the CUDA
+    and the Meta implementations allocate with it: ``torch.empty_like`` keeps the strides of a dense input (channels_last,
+    a transposed map, a (B,1,H,W) tensor that passes for both formats), which is not what the kernels write."""
+    return t.new_empty(t.shape, dtype=t.dtype if dtype is None else dtype)
+
+
 def _check_pair(a: torch.Tensor, b: torch.Tensor, what: str):
     if a.dim() != 4 or b.dim() != 4:
         raise RuntimeError("%s: expected 4-D NCHW tensors, got %s and %s"
@@ -243,8 +251,8 @@ def _correlation_backward_cuda(input1, input2, gradOutput, pad_size, kernel_size
         raise RuntimeError("%s: gradOutput shape %s, expected %s"
                            % (what, tuple(gradOutput.shape), (B, oc, oh, ow)))
     go = gradOutput.to(dtype=x1.dtype).contiguous()
-    g1 = torch.empty_like(x1)
-    g2 = torch.empty_like(x2)
+    g1 = _fresh_like(x1)
+    g2 = _fresh_like(x2)
     if x1.numel() == 0:
         return [g1, g2]
     with torch.cuda.device(x1.device):
@@ -257,7 +265,7 @@ def _correlation_backward_cuda(input1, input2, gradOutput, pad_size, kernel_size
 
 
 def _correlation_backward_meta(input1, input2, gradOutput, *_):
-    return [torch.empty_like(input1), torch.empty_like(input2)]
+    return [_fresh_like(input1), _fresh_like(input2)]
 
 
 def _correlation_backward_leaky_cuda(input1, input2, grad_buffer, fwd_buffer, channel_offset, pad_size,
@@ -295,7 +303,7 @@ def _correlation_backward_leaky_cuda(input1, input2, grad_buffer, fwd_buffer, ch
     # the real batch stride always (the C ABI reads 0 as "dense": never hand it a Python-side 0)
     go_bs = go.stride(0) if B > 1 else go.shape[1] * oh * ow
     fo_bs = fo.stride(0) if B > 1 else fo.shape[1] * oh * ow
-    g1, g2 = torch.empty_like(x1), torch.empty_like(x2)
+    g1, g2 = _fresh_like(x1), _fresh_like(x2)
     if x1.numel() == 0:
         return [g1, g2]
     lib = _lib.get()
@@ -351,7 +359,7 @@ def _flow_warp_run(image, flow, pad_mode, interp_mode, want_ctx, what):
     code = _dtype_code(image, what)
     img = image.contiguous()
     flo = _flow_for(img, flow)
-    out = torch.empty_like(img)
+    out = _fresh_like(img)
     B, C, H, W = img.shape
     lib = _lib.get()
     ctx_bytes = lib.cerberus_flow_warp_context_bytes(B, H, W) if want_ctx else 0
@@ -393,7 +401,7 @@ def _warp_context_bytes(B, H, W):
 def _flow_warp_ctx_meta(image, flow, pad_mode, interp_mode):
     B, _, H, W = image.shape
     n = (_warp_context_bytes(B, H, W) + 7) // 8
-    return torch.empty_like(image), image.new_empty((n,), dtype=torch.int64)
+    return _fresh_like(image), image.new_empty((n,), dtype=torch.int64)
 
 
 def _flow_warp_backward_run(image, flow, context, grad_out, pad_mode, interp_mode, need_image,
@@ -406,8 +414,8 @@ def _flow_warp_backward_run(image, flow, context, grad_out, pad_mode, interp_mod
     if go.shape != img.shape:
         raise RuntimeError("%s: grad_out shape %s, expected %s"
                            % (what, tuple(go.shape), tuple(img.shape)))
-    gi = torch.empty_like(img) if need_image else img.new_empty(0)
-    gf = torch.empty_like(flo) if need_flow else flo.new_empty(0)
+    gi = _fresh_like(img) if need_image else img.new_empty(0)
+    gf = _fresh_like(flo) if need_flow else flo.new_empty(0)
     if img.numel() == 0 or not (need_image or need_flow):
         return [gi, gf]
     B, C, H, W = img.shape
@@ -449,6 +457,15 @@ def _flow_warp_backward_ctx_cuda(image, flow, context, grad_out, pad_mode, inter
                                  need_image, need_flow) -> List[torch.Tensor]:
     return _flow_warp_backward_run(image, flow, context, grad_out, pad_mode, interp_mode,
                                    need_image, need_flow, "cerberus::flow_warp_backward_ctx")
+
+
+def _flow_warp_backward_meta(image, flow, need_image, need_flow):
+    """What ``_flow_warp_backward_run`` returns: grad_image like the image, grad_flow in the dtype ``_flow_for`` hands the
+    kernels (fp32 beside a 16-bit image, else the image's), and an empty (0,) tensor for a gradient that is not asked for."""
+    keep = flow.dtype == torch.float32 and image.dtype in (torch.float16, torch.bfloat16)
+    fdtype = flow.dtype if keep else image.dtype
+    return [_fresh_like(image) if need_image else image.new_empty(0),
+            _fresh_like(flow, fdtype) if need_flow else flow.new_empty(0, dtype=fdtype)]
 
 
 # ----------------------------------------------------------------------------
@@ -563,7 +580,7 @@ def _area_pyramid_cuda(image, sizes) -> List[torch.Tensor]:
         raise RuntimeError("%s: output sizes must be positive, got %s" % (what, pairs))
     # a scale of the image's own size is a COPY (F.interpolate returns one; a custom op must not return an alias of
     # its input: ADVICE r5) -- unFlowLoss asks for it at most once per step and only on pyramids that start at 1/1
-    outs = [x.clone() if (h, w) == (H, W) else x.new_empty((B, C, h, w)) for h, w in pairs]
+    outs = [x.clone(memory_format=torch.contiguous_format) if (h, w) == (H, W) else x.new_empty((B, C, h, w)) for h, w in pairs]
     todo = [(o, hw) for o, hw in zip(outs, pairs) if hw != (H, W) and o.numel()]
     if not todo:
         return outs
@@ -656,7 +673,7 @@ def _photometric_loss_backward_cuda(im_orig, im_recons, grad_loss, l1_weight, ss
         if not need:
             outs.append(a.new_empty((0,)))
             continue
-        grad = torch.empty_like(second)
+        grad = _fresh_like(second)
         with torch.cuda.device(a.device):
             rc = lib.cerberus_photometric_loss_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H, W,
                                                         float(l1_weight), float(ssim_weight), 0, _stream_ptr(a))
@@ -666,8 +683,8 @@ def _photometric_loss_backward_cuda(im_orig, im_recons, grad_loss, l1_weight, ss
 
 
 def _photometric_loss_backward_meta(im_orig, im_recons, grad_loss, l1_weight, ssim_weight, need_orig, need_recons):
-    return [torch.empty_like(im_orig) if need_orig else im_orig.new_empty((0,)),
-            torch.empty_like(im_recons) if need_recons else im_recons.new_empty((0,))]
+    return [_fresh_like(im_orig) if need_orig else im_orig.new_empty((0,)),
+            _fresh_like(im_recons) if need_recons else im_recons.new_empty((0,))]
 
 
 def _smoothness_check(flow, image, degree, what):
@@ -700,7 +717,7 @@ def _edge_smoothness_backward_cuda(flow, image, grad_loss, alpha, degree):
     f, img = flow.contiguous(), image.contiguous()
     g = _grad_scalar(grad_loss, f, what)
     B, Cf, H, W = f.shape
-    grad = torch.empty_like(f)
+    grad = _fresh_like(f)
     with torch.cuda.device(f.device):
         rc = _lib.get().cerberus_edge_smoothness_backward(f.data_ptr(), img.data_ptr(), g.data_ptr(), grad.data_ptr(), B, Cf,
                                                           img.shape[1], H, W, float(alpha), int(degree), 0, _stream_ptr(f))
@@ -771,7 +788,7 @@ def _census_loss_backward_cuda(im, im_warp, grad_loss, max_distance, need_im, ne
         if not need:
             outs.append(a.new_empty((0,)))
             continue
-        grad = torch.empty_like(second)
+        grad = _fresh_like(second)
         with torch.cuda.device(a.device):
             rc = lib.cerberus_census_loss_backward(first.data_ptr(), second.data_ptr(), g.data_ptr(), grad.data_ptr(), B, H, W,
                                                    int(max_distance), 0, _stream_ptr(a))
@@ -781,8 +798,8 @@ def _census_loss_backward_cuda(im, im_warp, grad_loss, max_distance, need_im, ne
 
 
 def _census_loss_backward_meta(im, im_warp, grad_loss, max_distance, need_im, need_warp):
-    return (torch.empty_like(im) if need_im else im.new_empty((0,)),
-            torch.empty_like(im_warp) if need_warp else im_warp.new_empty((0,)))
+    return (_fresh_like(im) if need_im else im.new_empty((0,)),
+            _fresh_like(im_warp) if need_warp else im_warp.new_empty((0,)))
 
 
 # the occlusion masks (UnFlowLoss.py:34-81, :96-117), csrc/occlusion.hip: forward only
@@ -876,7 +893,7 @@ def _reproject_warp_cuda(image, depth, inv_K, proj, eps):
     _reproject_check(image, depth, inv_K, proj, what)
     img, d, k, p = image.contiguous(), depth.contiguous(), inv_K.contiguous(), proj.contiguous()
     B, C, H, W = img.shape
-    out = torch.empty_like(img)
+    out = _fresh_like(img)
     with torch.cuda.device(img.device):
         rc = _lib.get().cerberus_reproject_warp_forward(img.data_ptr(), d.data_ptr(), k.data_ptr(), p.data_ptr(), out.data_ptr(),
                                                         B, C, H, W, float(eps), 0, _stream_ptr(img))
@@ -889,7 +906,7 @@ def _reproject_warp_backward_cuda(image, depth, inv_K, proj, grad_out, eps):
     _reproject_check(image, depth, inv_K, proj, what, grad_out)
     img, d, k, p, g = (t.contiguous() for t in (image, depth, inv_K, proj, grad_out))
     B, C, H, W = img.shape
-    grad = torch.empty_like(d)
+    grad = _fresh_like(d)
     with torch.cuda.device(img.device):
         rc = _lib.get().cerberus_reproject_warp_backward(img.data_ptr(), d.data_ptr(), k.data_ptr(), p.data_ptr(), g.data_ptr(),
                                                          grad.data_ptr(), B, C, H, W, float(eps), 0, _stream_ptr(img))
@@ -966,11 +983,14 @@ def _seg_cross_entropy_backward_cuda(logits, target, weight, lse, state, grad_lo
             raise RuntimeError("%s: %s must be the float32 %s tensor of the forward, got %s %s" % (what, name, shape, t.dtype,
                                                                                                   tuple(t.shape)))
     x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    # named, so that each copy lives until the launch is enqueued: a temporary ``v.contiguous().data_ptr()`` is freed at once,
+    # and the next copy may be handed its block while the first pointer is still to be read
+    ls, st = lse.contiguous(), state.contiguous()
     g = _grad_scalar(grad_loss, x, what)
-    grad = torch.empty_like(x)          # every element is written by the kernel
+    grad = _fresh_like(x)          # every element is written by the kernel
     with torch.cuda.device(x.device):
-        rc = _lib.get().cerberus_seg_cross_entropy_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), lse.contiguous().data_ptr(),
-                                                            state.contiguous().data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H,
+        rc = _lib.get().cerberus_seg_cross_entropy_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), ls.data_ptr(),
+                                                            st.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H,
                                                             W, int(ignore_index), 0, _stream_ptr(x))
     _lib.check(rc, what)
     return grad
@@ -1031,11 +1051,12 @@ def _seg_ohem_backward_cuda(logits, target, weight, prob, lse, state, grad_loss,
             raise RuntimeError("%s: %s must be the float32 %s tensor of the forward, got %s %s" % (what, name, shape, t.dtype,
                                                                                                   tuple(t.shape)))
     x, t, w = logits.contiguous(), target.contiguous(), weight.contiguous()
+    pr, ls, st = prob.contiguous(), lse.contiguous(), state.contiguous()      # named: alive until the launch (see above)
     g = _grad_scalar(grad_loss, x, what)
-    grad = torch.empty_like(x)          # every element is written by the kernel
+    grad = _fresh_like(x)          # every element is written by the kernel
     with torch.cuda.device(x.device):
-        rc = _lib.get().cerberus_seg_ohem_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), prob.contiguous().data_ptr(),
-                                                   lse.contiguous().data_ptr(), state.contiguous().data_ptr(), g.data_ptr(),
+        rc = _lib.get().cerberus_seg_ohem_backward(x.data_ptr(), t.data_ptr(), w.data_ptr(), pr.data_ptr(),
+                                                   ls.data_ptr(), st.data_ptr(), g.data_ptr(),
                                                    grad.data_ptr(), B, C, H, W, int(ignore_index), 0, _stream_ptr(x))
     _lib.check(rc, what)
     return grad
@@ -1146,11 +1167,14 @@ def _rmi_moments_backward_cuda(logits, target, la_map, pr_map, means, state, gra
                                                                                            tuple(v.shape)))
     x, t = logits.contiguous(), target.contiguous()
     g = _grad_scalar(grad_bce, x, what)
-    grad = torch.empty_like(x)          # every element is written by the kernel
-    ptr = lambda v: v.contiguous().data_ptr() if do_rmi else None
+    grad = _fresh_like(x)          # every element is written by the kernel
+    # named: every copy lives until the launch is enqueued (see _seg_cross_entropy_backward_cuda)
+    st = state.contiguous()
+    la, pr, mu, gp, glp = (v.contiguous() for v in (la_map, pr_map, means, grad_pr_cov, grad_la_pr_cov))
+    ptr = lambda v: v.data_ptr() if do_rmi else None
     with torch.cuda.device(x.device):
-        rc = _lib.get().cerberus_rmi_backward(x.data_ptr(), t.data_ptr(), state.contiguous().data_ptr(), ptr(la_map), ptr(pr_map),
-                                              ptr(means), g.data_ptr(), ptr(grad_pr_cov), ptr(grad_la_pr_cov), grad.data_ptr(), B, C,
+        rc = _lib.get().cerberus_rmi_backward(x.data_ptr(), t.data_ptr(), st.data_ptr(), ptr(la), ptr(pr),
+                                              ptr(mu), g.data_ptr(), ptr(gp), ptr(glp), grad.data_ptr(), B, C,
                                               H, W, int(radius), int(pool), int(bool(do_rmi)), 0, _stream_ptr(x))
     _lib.check(rc, what)
     return grad
@@ -1240,11 +1264,11 @@ def _inv_huber_backward_cuda(pred, gt, state, grad_loss):
     if state.dtype != torch.float32 or state.device != pred.device or tuple(state.shape) != (4,):
         raise RuntimeError("%s: state must be the float32 (4,) tensor of the forward, got %s %s" % (what, state.dtype,
                                                                                                    tuple(state.shape)))
-    p, g = pred.contiguous(), gt.contiguous()
+    p, g, st = pred.contiguous(), gt.contiguous(), state.contiguous()
     gl = _grad_scalar(grad_loss, p, what)
-    grad = torch.empty_like(p)          # every element is written by the kernel
+    grad = _fresh_like(p)          # every element is written by the kernel
     with torch.cuda.device(p.device):
-        rc = _lib.get().cerberus_inv_huber_backward(p.data_ptr(), g.data_ptr(), state.contiguous().data_ptr(), gl.data_ptr(),
+        rc = _lib.get().cerberus_inv_huber_backward(p.data_ptr(), g.data_ptr(), st.data_ptr(), gl.data_ptr(),
                                                     grad.data_ptr(), B, h, w, H, W, 0, _stream_ptr(p))
     _lib.check(rc, what)
     return grad
@@ -1430,7 +1454,7 @@ def _center_peaks_cuda(heatmap, threshold, nms_kernel):
     if nms_kernel < 1 or nms_kernel % 2 == 0 or nms_kernel > CENTER_PEAKS_MAX_KERNEL:
         raise RuntimeError("%s: nms_kernel must be odd and lie in 1..%d, got %d" % (what, CENTER_PEAKS_MAX_KERNEL, nms_kernel))
     x = heatmap.contiguous()
-    out = torch.empty_like(x)               # every element is written by the kernel; the input never is
+    out = _fresh_like(x)               # every element is written by the kernel; the input never is
     with torch.cuda.device(x.device):
         rc = _lib.get().cerberus_center_peaks(x.data_ptr(), out.data_ptr(), B, H, W, ctypes.c_float(threshold), int(nms_kernel), 0,
                                               _stream_ptr(x))
@@ -1661,16 +1685,17 @@ def _panoptic_loss_backward_cuda(center_pred, center_tgt, center_mask, offset_pr
                                                                                                    tuple(state.shape)))
     ts = [t.contiguous() if t is not None else None for t in (center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask)]
     gl = _grad_scalar(grad_loss, ts[0], what)
-    gc, go = torch.empty_like(ts[0]), torch.empty_like(ts[3])       # every element is written by the kernel
+    st = state.contiguous()
+    gc, go = _fresh_like(ts[0]), _fresh_like(ts[3])       # every element is written by the kernel
     with torch.cuda.device(ts[0].device):
-        rc = _lib.get().cerberus_panoptic_loss_backward(*[_ptr(t) for t in ts], state.contiguous().data_ptr(), gl.data_ptr(),
+        rc = _lib.get().cerberus_panoptic_loss_backward(*[_ptr(t) for t in ts], st.data_ptr(), gl.data_ptr(),
                                                         gc.data_ptr(), go.data_ptr(), B, H, W, int(mode), 0, _stream_ptr(ts[0]))
     _lib.check(rc, what)
     return gc, go
 
 
 def _panoptic_loss_backward_meta(center_pred, center_tgt, center_mask, offset_pred, offset_tgt, offset_mask, state, grad_loss, mode):
-    return torch.empty_like(center_pred), torch.empty_like(offset_pred)
+    return _fresh_like(center_pred), _fresh_like(offset_pred)
 
 
 def _no_cpu(name):
@@ -1720,19 +1745,19 @@ _def.impl("seg_cross_entropy", _seg_cross_entropy_cuda, "CUDA")
 _def.impl("seg_cross_entropy", _seg_cross_entropy_meta, "Meta")
 _def.impl("seg_cross_entropy", _no_cpu("seg_cross_entropy"), "CPU")
 _def.impl("seg_cross_entropy_backward", _seg_cross_entropy_backward_cuda, "CUDA")
-_def.impl("seg_cross_entropy_backward", lambda x, t, w, lse, st, g, i: torch.empty_like(x), "Meta")
+_def.impl("seg_cross_entropy_backward", lambda x, t, w, lse, st, g, i: _fresh_like(x), "Meta")
 _def.impl("seg_cross_entropy_backward", _no_cpu("seg_cross_entropy_backward"), "CPU")
 _def.impl("rmi_moments", _rmi_moments_cuda, "CUDA")
 _def.impl("rmi_moments", _rmi_moments_meta, "Meta")
 _def.impl("rmi_moments", _no_cpu("rmi_moments"), "CPU")
 _def.impl("rmi_moments_backward", _rmi_moments_backward_cuda, "CUDA")
-_def.impl("rmi_moments_backward", lambda x, *a: torch.empty_like(x), "Meta")
+_def.impl("rmi_moments_backward", lambda x, *a: _fresh_like(x), "Meta")
 _def.impl("rmi_moments_backward", _no_cpu("rmi_moments_backward"), "CPU")
 _def.impl("seg_ohem_cross_entropy", _seg_ohem_cuda, "CUDA")
 _def.impl("seg_ohem_cross_entropy", _seg_ohem_meta, "Meta")
 _def.impl("seg_ohem_cross_entropy", _no_cpu("seg_ohem_cross_entropy"), "CPU")
 _def.impl("seg_ohem_cross_entropy_backward", _seg_ohem_backward_cuda, "CUDA")
-_def.impl("seg_ohem_cross_entropy_backward", lambda x, t, w, p, lse, st, g, i: torch.empty_like(x), "Meta")
+_def.impl("seg_ohem_cross_entropy_backward", lambda x, t, w, p, lse, st, g, i: _fresh_like(x), "Meta")
 _def.impl("seg_ohem_cross_entropy_backward", _no_cpu("seg_ohem_cross_entropy_backward"), "CPU")
 _def.impl("class_histogram", _class_histogram_cuda, "CUDA")
 _def.impl("class_histogram", lambda t, c, i: t.new_empty((c,), dtype=torch.int64), "Meta")
@@ -1744,7 +1769,7 @@ _def.impl("inv_huber", _inv_huber_cuda, "CUDA")
 _def.impl("inv_huber", _inv_huber_meta, "Meta")
 _def.impl("inv_huber", _no_cpu("inv_huber"), "CPU")
 _def.impl("inv_huber_backward", _inv_huber_backward_cuda, "CUDA")
-_def.impl("inv_huber_backward", lambda p, g, st, gl: torch.empty_like(p), "Meta")
+_def.impl("inv_huber_backward", lambda p, g, st, gl: _fresh_like(p), "Meta")
 _def.impl("inv_huber_backward", _no_cpu("inv_huber_backward"), "CPU")
 _def.impl("seg_confusion", _seg_confusion_cuda, "CUDA")
 _def.impl("seg_confusion", _seg_confusion_meta, "Meta")
@@ -1759,7 +1784,7 @@ _def.impl("warp_sad", _warp_sad_cuda, "CUDA")
 _def.impl("warp_sad", lambda im, src, fl: im.new_empty((im.shape[0],), dtype=torch.float64), "Meta")
 _def.impl("warp_sad", _no_cpu("warp_sad"), "CPU")
 _def.impl("center_peaks", _center_peaks_cuda, "CUDA")
-_def.impl("center_peaks", lambda h, t, k: torch.empty_like(h), "Meta")
+_def.impl("center_peaks", lambda h, t, k: _fresh_like(h), "Meta")
 _def.impl("center_peaks", _no_cpu("center_peaks"), "CPU")
 _def.impl("group_pixels", _group_pixels_cuda, "CUDA")
 _def.impl("group_pixels", _group_pixels_meta, "Meta")
@@ -1777,7 +1802,7 @@ _def.impl("panoptic_loss_backward", _panoptic_loss_backward_cuda, "CUDA")
 _def.impl("panoptic_loss_backward", _panoptic_loss_backward_meta, "Meta")
 _def.impl("panoptic_loss_backward", _no_cpu("panoptic_loss_backward"), "CPU")
 _def.impl("edge_smoothness_backward", _edge_smoothness_backward_cuda, "CUDA")
-_def.impl("edge_smoothness_backward", lambda f, i, g, al, d: torch.empty_like(f), "Meta")
+_def.impl("edge_smoothness_backward", lambda f, i, g, al, d: _fresh_like(f), "Meta")
 _def.impl("edge_smoothness_backward", _no_cpu("edge_smoothness_backward"), "CPU")
 _def.impl("correlation_backward", _correlation_backward_cuda, "CUDA")
 _def.impl("correlation_backward", _correlation_backward_meta, "Meta")
@@ -1799,20 +1824,16 @@ _def.impl("area_resize", _area_resize_cuda, "CUDA")
 _def.impl("area_resize", lambda x, h, w: x.new_empty((x.shape[0], x.shape[1], h, w)), "Meta")
 _def.impl("area_resize", _no_cpu("area_resize"), "CPU")
 _def.impl("flow_warp", _flow_warp_cuda, "CUDA")
-_def.impl("flow_warp", lambda image, flow, p, m: torch.empty_like(image), "Meta")
+_def.impl("flow_warp", lambda image, flow, p, m: _fresh_like(image), "Meta")
 _def.impl("flow_warp", _no_cpu("flow_warp"), "CPU")
 _def.impl("flow_warp_backward", _flow_warp_backward_cuda, "CUDA")
-_def.impl("flow_warp_backward",
-          lambda image, flow, go, p, m, ni, nf: [torch.empty_like(image), torch.empty_like(flow)],
-          "Meta")
+_def.impl("flow_warp_backward", lambda image, flow, go, p, m, ni, nf: _flow_warp_backward_meta(image, flow, ni, nf), "Meta")
 _def.impl("flow_warp_backward", _no_cpu("flow_warp_backward"), "CPU")
 _def.impl("flow_warp_ctx", _flow_warp_ctx_cuda, "CUDA")
 _def.impl("flow_warp_ctx", _flow_warp_ctx_meta, "Meta")
 _def.impl("flow_warp_ctx", _no_cpu("flow_warp_ctx"), "CPU")
 _def.impl("flow_warp_backward_ctx", _flow_warp_backward_ctx_cuda, "CUDA")
-_def.impl("flow_warp_backward_ctx",
-          lambda image, flow, ctx, go, p, m, ni, nf: [torch.empty_like(image),
-                                                      torch.empty_like(flow)], "Meta")
+_def.impl("flow_warp_backward_ctx", lambda image, flow, ctx, go, p, m, ni, nf: _flow_warp_backward_meta(image, flow, ni, nf), "Meta")
 _def.impl("flow_warp_backward_ctx", _no_cpu("flow_warp_backward_ctx"), "CPU")
 
 
