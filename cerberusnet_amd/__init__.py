@@ -17,6 +17,10 @@ from .loss_functions.seg_losses import FocalLoss2D, SegCrossEntropy, class_balan
 from .loss_functions.UnFlowLoss import (TernaryLoss, area_pyramid, area_resize, census_loss, edge_smoothness, flow_warp,
                                          get_corresponding_map, get_occu_mask_backward, get_occu_mask_bidirection, mesh_grid,
                                          norm_grid, photometric_loss)
+from . import ops_ocr  # noqa: F401  (registers torch.ops.cerberus_ocr.*)
+from .nnet_models.ocr_utils import BNReLU, ObjectAttentionBlock, SpatialGather_Module, SpatialOCR_Module, scale_as
+from .nnet_models.ocrnet import OCR_block, OCRNetHead
+from .ops_ocr import object_attention, spatial_gather
 from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
 from .utilities.panoptic_targets import PanopticTargetGenerator, panoptic_targets
 
@@ -27,4 +31,6 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "SegCrossEntropy", "seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss",
            "MixSoftmaxCrossEntropyOHEMLoss", "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
-           "PanopticMetric", "deeplab_panoptic_loss", "DeeplabPanopticLoss", "panoptic_targets", "PanopticTargetGenerator", "ops"]
+           "PanopticMetric", "deeplab_panoptic_loss", "DeeplabPanopticLoss", "panoptic_targets", "PanopticTargetGenerator", "ops",
+           "BNReLU", "scale_as", "SpatialGather_Module", "ObjectAttentionBlock", "SpatialOCR_Module", "OCR_block", "OCRNetHead",
+           "spatial_gather", "object_attention", "ops_ocr"]

@@ -87,6 +87,11 @@ PROTOTYPES = {
     "cerberus_rmi_workspace_bytes": (_I64, [_I] * 5),
     "cerberus_rmi_forward": (_I, [_P] * 11 + [_I64] + [_I] * 8 + [_P]),
     "cerberus_rmi_backward": (_I, [_P] * 10 + [_I] * 8 + [_P]),
+    "cerberus_ocr_workspace_bytes": (_I64, [_I] * 4),
+    "cerberus_ocr_gather_forward": (_I, [_P] * 5 + [_I64] + [_I] * 4 + [ctypes.c_float, _I, _P]),
+    "cerberus_ocr_gather_backward": (_I, [_P] * 7 + [_I64] + [_I] * 4 + [ctypes.c_float, _I, _P]),
+    "cerberus_ocr_attention_forward": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float, _I, _P]),
+    "cerberus_ocr_attention_backward": (_I, [_P] * 10 + [_I64] + [_I] * 4 + [ctypes.c_float, _I, _P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

@@ -2,6 +2,9 @@ from .pwcnet_sfd import PWCNetHead
 from .pwcnet_modules import FlowEstimatorDense, FlowEstimatorLite, ContextNetwork
 from .hrnetv2 import HighResolutionNet, hrnet_config
 from .cerberus import CerberusBase, cerberus_flow_config
+from .ocr_utils import BNReLU, ObjectAttentionBlock, SpatialGather_Module, SpatialOCR_Module, scale_as
+from .ocrnet import OCR_block, OCRNetHead
 
 __all__ = ["PWCNetHead", "FlowEstimatorDense", "FlowEstimatorLite", "ContextNetwork",
-           "HighResolutionNet", "hrnet_config", "CerberusBase", "cerberus_flow_config"]
+           "HighResolutionNet", "hrnet_config", "CerberusBase", "cerberus_flow_config",
+           "BNReLU", "scale_as", "SpatialGather_Module", "ObjectAttentionBlock", "SpatialOCR_Module", "OCR_block", "OCRNetHead"]

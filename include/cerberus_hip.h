@@ -576,6 +576,41 @@ int cerberus_rmi_backward(const void *logits, const void *target, const void *st
                           const void *grad_la_pr_cov, void *grad_logits, int B, int C, int H, int W, int radius, int pool,
                           int do_rmi, int dtype, void *stream);
 
+/* The OCR segmentation head's two own steps (additions only: no ABI bump): SpatialGather_Module and the core of
+ * ObjectAttentionBlock (nnet_models/ocr_utils.py), fp32, forward and backward.  HW = H * W; R (K for the gather) in 1..32.
+ *
+ * Spatial gather:  p[b,k,:] = softmax over the HW pixels of scale * logits[b,k,:];  context[b,c,k] = sum_p p[b,k,p] feats[b,c,p]
+ *   feats (B,C,HW), logits (B,K,HW) -> context (B,C,K), lse (B,K) = log sum_p exp(scale * logits[b,k,p])
+ *   backward: grad_feats[b,c,p] = sum_k p[b,k,p] g[b,c,k];
+ *             grad_logits[b,k,p] = scale p[b,k,p] (sum_c g[b,c,k] feats[b,c,p] - sum_c g[b,c,k] context[b,c,k]),  g = grad_context
+ *   The backward forms p from the plane's maximum and sum, which it computes again from the logits (a pass over K / C of the bytes
+ *   of the features): exp(x - lse) would carry the rounding of lse, half an ulp of a number near log(HW) + max, into every
+ *   probability of the plane.
+ * Object attention:  a[b,:,p] = softmax over r of scale * sum_c query[b,c,p] key[b,c,r];  context[b,c,p] = sum_r a[b,r,p] value[b,c,r]
+ *   query (B,C,HW), key / value (B,C,R) -> context (B,C,HW), attn (B,R,HW)
+ *   backward: da[r] = sum_c g[b,c,p] value[b,c,r];  dsim = a (da - sum_r a da), written to the caller's (B,R,HW) buffer `dsim`;
+ *             grad_query[b,c,p] = scale sum_r dsim[b,r,p] key[b,c,r];  grad_key[b,c,r] = scale sum_p dsim[b,r,p] query[b,c,p];
+ *             grad_value[b,c,r] = sum_p a[b,r,p] g[b,c,p]
+ * Every sum over pixels is one partial per chunk of 256 pixels, added in chunk order by a second launch: no floating-point
+ * atomics, the same bits on every run and for any alignment of the base pointers (no alignment is required).  Every output
+ * element is written (no zero-fill needed); no host synchronisation: capturable.
+ *   workspace : cerberus_ocr_workspace_bytes(B,C,R,HW) bytes (0 for sizes the calls reject), 16-byte aligned, fully overwritten;
+ *               the gather forward and backward and the attention backward take it, the attention forward needs none.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B, C, R or HW <= 0 CERB_EINVAL; R > 32
+ * CERB_EUNSUPPORTED; HW > 2^31 - 1025, or C R, B ceil(HW / 256), B ceil(C R / 256) past 2^31 - 1 CERB_ETOOLARGE; a null pointer, a
+ * workspace that is misaligned or too small CERB_EINVAL -- all before any launch. */
+int64_t cerberus_ocr_workspace_bytes(int B, int C, int R, int HW);
+int cerberus_ocr_gather_forward(const void *feats, const void *logits, void *context, void *lse, void *workspace,
+                                int64_t workspace_bytes, int B, int C, int K, int HW, float scale, int dtype, void *stream);
+int cerberus_ocr_gather_backward(const void *feats, const void *logits, const void *context, const void *grad_context,
+                                 void *grad_feats, void *grad_logits, void *workspace, int64_t workspace_bytes, int B, int C, int K,
+                                 int HW, float scale, int dtype, void *stream);
+int cerberus_ocr_attention_forward(const void *query, const void *key, const void *value, void *context, void *attn, int B, int C,
+                                   int R, int HW, float scale, int dtype, void *stream);
+int cerberus_ocr_attention_backward(const void *grad_context, const void *query, const void *key, const void *value, const void *attn,
+                                    void *grad_query, void *grad_key, void *grad_value, void *dsim, void *workspace,
+                                    int64_t workspace_bytes, int B, int C, int R, int HW, float scale, int dtype, void *stream);
+
 /* The device side of the panoptic metric (additions only: no ABI bump): what the reference's PanopticMetric
  * (nnet_training/statistics/panoptic.py) and utilities/panoptic_post_processing.py do to the centre heat map, the offset map and
  * the id / class maps of every image.  Forward only, no host synchronisation, no floating-point atomics: capturable and
