@@ -1422,7 +1422,11 @@ int fwd_pick(const void *in1, const void *in2, void *out, const CorrGeom &g, flo
     // round 6: W % 8 == 0 and C <= 64 take the column walk (LDS-DMA, transposing reads); corr_fwd_variant 20 keeps the
     // register-staged form of rounds 4-5 (also: other widths, 65 .. 128 channels), 26 the walk's stand-still form (C <= 32)
     const int v = option(OPT_CORR_FWD_VARIANT);
-    const bool cells = g.W % 8 == 0 && v != 20;
+    // The walk / tr kernels copy 16-byte cells by LDS-DMA at offsets that are multiples of 16 bytes (W % 8 == 0): with both
+    // inputs on 16 bytes every transfer of the walk is naturally aligned.  The caller's gate asks for 8 (a 4-element
+    // group); an input that passes it at 8 mod 16 keeps the register-staged form, whose loads are 8-byte ones
+    const bool cell_aligned = ((reinterpret_cast<uintptr_t>(in1) | reinterpret_cast<uintptr_t>(in2)) & 15) == 0;
+    const bool cells = g.W % 8 == 0 && v != 20 && cell_aligned;
     if (g.C <= 32) {
         if (cells && v == 26)
             return launch_fwd_mfma_tr<FwdTrCfg<2>, T>("corr_fwd_d4_mfma_tr_4x64", in1, in2, out, g, slope, obs, s);

@@ -59,6 +59,20 @@ enum cerb_interp_mode { CERB_INTERP_BILINEAR = 0, CERB_INTERP_NEAREST = 1 };
 #define CERB_EUNSUPPORTED -5  /* valid but not implemented (reflection pad in the f2 fused warp) */
 #define CERB_ETOOLARGE    -6  /* a dimension exceeds 32-bit launch / index limits       */
 
+/* Pointer alignment (tests/test_alignment_gpu.py):
+ *   Tensor pointers -- inputs, outputs, gradients -- need the alignment of their element type and no more.  The
+ *   correlation, flow_warp and flow_upsample calls test each pointer and take their vector / LDS-DMA / matrix-core kernels
+ *   where the pointers allow it: 16 bytes on every tensor for fp32; 8 bytes for fp16 / bf16 (16 on input1 and input2 for
+ *   the matrix-core forward's column walk).  flow_warp with a 16-bit image: 16 bytes on image and grad_image, 8 on out, 4 on
+ *   grad_out, and 8 on flow and grad_flow whatever the flow's type (fp32 or 16-bit); with an fp32 image: 16 on image and
+ *   grad_image.  Any other pointer takes a slower kernel: the result stays within the same bound of the reference, and has
+ *   the same bits wherever the kernel is the same.  What torch's allocator returns passes every test.
+ *   A warp context must be 16-byte aligned: CERB_EINVAL otherwise, before any launch.  A workspace must be 16-byte aligned
+ *   unless its comment names less, and is rejected with CERB_EINVAL otherwise, with two exceptions that fall back instead
+ *   and return CERB_OK: cerberus_flow_warp_backward treats a workspace that is misaligned or too small as no workspace
+ *   (without a context: the scatter kernel, global float atomics, grad_image's summation order not fixed), and
+ *   cerberus_warp_correlation_forward takes its one-launch form. */
+
 int cerberus_abi_version(void);
 
 /* Human-readable text for a return code of any function below. */
@@ -195,7 +209,8 @@ int cerberus_warp_correlation_forward(const void *input1, const void *input2, co
  *   workspace  : caller-owned device scratch of at least
  *                cerberus_flow_warp_backward_workspace_bytes(B,C,H,W) bytes (16-byte
  *                aligned, contents irrelevant), private to this call until it completes;
- *                only needed when context is NULL.
+ *                only needed when context is NULL.  A workspace that is NULL, too small or not
+ *                16-byte aligned is no error: the call then runs as "with neither" above.
  * Every pad_mode x interp_mode pair is differentiable, with ATen's rules (align_corners = false):
  * reflection multiplies the position gradient by the reflection's sign and zeroes it where the
  * reflected position clips onto an edge; nearest adds grad_out to the nearbyint tap (ties to

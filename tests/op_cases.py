@@ -13,7 +13,8 @@ produced are zeros of the shapes ``OUTPUTS`` states for that forward.
 
 No layout shifts a tensor's start address: every view begins at offset 0 of its own buffer, so the binding's ``.contiguous()``
 copies are the only thing between a layout and the kernels, and the kernels see the pointers the rest of the suite gives them.
-Misaligned and offset views are not part of this table."""
+Misaligned and offset views are not part of this table: tests/alignment_cases.py puts its arguments into such views
+(``test_same_bits_from_an_offset_view``), and tests/test_alignment_gpu.py holds the hot-path kernels at every alignment gate."""
 import numpy as np
 import torch
 

@@ -9,12 +9,18 @@
    kernels on the same values, and the kernels are bit-reproducible run to run.  That premise is asserted first (two
    contiguous calls give equal bits); no op needed another shape or a tolerance for it.
 3. ``torch.library.opcheck``: schema, autograd registration, fake against real (sizes, strides, storage offsets, dtypes,
-   devices) and AOT dispatch.  ``AOT_EXCLUDED`` lists the (op, util) pairs that cannot pass, each with its reason."""
+   devices) and AOT dispatch.  ``AOT_EXCLUDED`` lists the (op, util) pairs that cannot pass, each with its reason.
+4. Same bits from an offset view: every tensor argument (and every upstream gradient) as a contiguous view that starts one
+   element off a 16-byte boundary inside a buffer whose other elements are NaN (tests/alignment_cases.py: ``embed``).  The
+   binding hands such a view's pointer to the kernels as it is, so their alignment gates decide; an op whose gate changes
+   the summation order would be listed in ``OFFSET_EXCLUDED`` with its reason and held to its reference bound instead.
+   (The correlation and warp kernels at every gate and shift: tests/test_alignment_gpu.py.)"""
 import pytest
 import torch
 
 import cerberusnet_amd  # noqa: F401  (registers the ops)
 import op_cases
+from alignment_cases import embed
 from op_cases import same_bits
 from test_op_contract_cpu import check_outputs, flat
 
@@ -30,6 +36,11 @@ AOT_EXCLUDED = {
         "center_points holds NaN for a table row without a centre (the reference's convention) and opcheck compares the "
         "eager with the compiled outputs by assert_close without equal_nan",
 }
+
+
+# op -> (why a misaligned pointer legitimately changes its summation order, the bound of the op's own test against its
+# reference); at most six (a test holds the cap)
+OFFSET_EXCLUDED = {}
 
 
 def call(name, args):
@@ -55,7 +66,8 @@ def upstream(out, k, layout, expanded):
     if expanded:
         w = op_cases.on(DEV, op_cases.hash_uniform(tuple(out.shape[1:]), 900 + k, dtype=dtype))
         return w.expand(out.shape)
-    return op_cases.lay(op_cases.on(DEV, op_cases.hash_uniform(tuple(out.shape), 900 + k, dtype=dtype)), layout)
+    full = op_cases.on(DEV, op_cases.hash_uniform(tuple(out.shape), 900 + k, dtype=dtype))
+    return embed(full, 1) if layout == "offset" else op_cases.lay(full, layout)
 
 
 def evaluate(name, args, differentiable, layout, materialise=False):
@@ -114,6 +126,34 @@ def test_same_bits_as_the_contiguous_call(name, layout):
         assert grad0[differentiable.index(i)].shape == plain[i].shape and bool(grad0[differentiable.index(i)].abs().sum() > 0)
 
 
+def offset_views(name, args):
+    """Every tensor argument one element off a 16-byte boundary, but for the arguments a binding takes in the form the forward
+    returned (``NO_LAYOUT``: the concat buffers, the warp context, which must be 16-byte aligned)."""
+    keep = op_cases.NO_LAYOUT.get(name, ())
+    return [embed(a, 1) if isinstance(a, torch.Tensor) and i not in keep else a for i, a in enumerate(args)]
+
+
+@pytest.mark.parametrize("name", list(op_cases.CASES))
+def test_same_bits_from_an_offset_view(name):
+    plain, differentiable = op_cases.case(name, DEV, "contiguous")
+    args = offset_views(name, plain)
+    for a, b in zip(args, plain):
+        if isinstance(a, torch.Tensor) and a is not b:
+            assert a.is_contiguous() and a.data_ptr() % 16 == a.element_size() % 16 and same_bits(a, b)
+    _, res0, grad0, wide0 = evaluate(name, plain, differentiable, "contiguous", materialise=True)
+    outs, res, grad, wide = evaluate(name, args, differentiable, "offset")
+    check_outputs(name, outs, "cuda")
+    if name in OFFSET_EXCLUDED:
+        bound = OFFSET_EXCLUDED[name][1]
+        for got, want in zip(res + grad + wide, res0 + grad0 + wide0):
+            scale = float(want.double().abs().max()) or 1.0
+            assert float((got.double() - want.double()).abs().max()) <= bound * scale, name
+        return
+    assert_same(name, "offset", "outputs", res, res0)
+    assert_same(name, "offset", "gradients", grad, grad0)
+    assert_same(name, "offset", "gradients (expanded)", wide, wide0)
+
+
 def test_a_non_contiguous_concat_buffer_is_rejected():
     for layout in ("channels_last", "sliced"):
         args, _ = op_cases.case("correlation_leaky_into", DEV, "contiguous")
@@ -135,3 +175,6 @@ def test_the_exclusion_table_is_small_and_names_real_ops():
     assert len(AOT_EXCLUDED) <= 4
     for (name, util), reason in AOT_EXCLUDED.items():
         assert name in op_cases.CASES and util == "test_aot_dispatch_static" and reason
+    assert len(OFFSET_EXCLUDED) <= 6
+    for name, (reason, bound) in OFFSET_EXCLUDED.items():
+        assert name in op_cases.CASES and reason and 0 < bound < 1
