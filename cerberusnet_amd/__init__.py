@@ -21,6 +21,9 @@ from . import ops_ocr  # noqa: F401  (registers torch.ops.cerberus_ocr.*)
 from .nnet_models.ocr_utils import BNReLU, ObjectAttentionBlock, SpatialGather_Module, SpatialOCR_Module, scale_as
 from .nnet_models.ocrnet import OCR_block, OCRNetHead
 from .ops_ocr import object_attention, spatial_gather
+from . import ops_detr  # noqa: F401  (registers torch.ops.cerberus_detr.*)
+from .loss_functions.detr_loss import DetrLoss, detr_set_loss
+from .nnet_models.detr import HungarianMatcher, pad_targets
 from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
 from .utilities.panoptic_targets import PanopticTargetGenerator, panoptic_targets
 
@@ -33,4 +36,5 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss", "MetricBase", "SegmentationMetric", "DepthMetric", "OpticFlowMetric",
            "PanopticMetric", "deeplab_panoptic_loss", "DeeplabPanopticLoss", "panoptic_targets", "PanopticTargetGenerator", "ops",
            "BNReLU", "scale_as", "SpatialGather_Module", "ObjectAttentionBlock", "SpatialOCR_Module", "OCR_block", "OCRNetHead",
-           "spatial_gather", "object_attention", "ops_ocr"]
+           "spatial_gather", "object_attention", "ops_ocr",
+           "ops_detr", "DetrLoss", "detr_set_loss", "HungarianMatcher", "pad_targets"]

@@ -92,6 +92,13 @@ PROTOTYPES = {
     "cerberus_ocr_gather_backward": (_I, [_P] * 7 + [_I64] + [_I] * 4 + [ctypes.c_float, _I, _P]),
     "cerberus_ocr_attention_forward": (_I, [_P] * 5 + [_I] * 4 + [ctypes.c_float, _I, _P]),
     "cerberus_ocr_attention_backward": (_I, [_P] * 10 + [_I64] + [_I] * 4 + [ctypes.c_float, _I, _P]),
+    "cerberus_detr_fused_ok": (_I, [_I] * 3),
+    "cerberus_detr_workspace_bytes": (_I64, [_I]),
+    "cerberus_detr_match_cost": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float] * 3 + [_I, _P]),
+    "cerberus_detr_lsap": (_I, [_P] * 4 + [_I] * 4 + [_P]),
+    "cerberus_detr_hungarian_match": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float] * 3 + [_I, _P]),
+    "cerberus_detr_set_loss_forward": (_I, [_P] * 11 + [_I64] + [_I] * 6 + [_P]),
+    "cerberus_detr_set_loss_backward": (_I, [_P] * 12 + [_I] * 6 + [_P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

@@ -1,5 +1,6 @@
 from .depth_losses import (BackprojectDepth, DepthAwareLoss, DepthReconstructionLossV1, InvHuberLoss, InvHuberLossPyr, Project3D,
                            ScaleInvariantError, inv_huber_loss, reproject_warp)
+from .detr_loss import DetrLoss, detr_set_loss
 from .ohem_losses import (MixSoftmaxCrossEntropyLoss, MixSoftmaxCrossEntropyOHEMLoss, SoftmaxCrossEntropyOHEMLoss,
                           seg_ohem_cross_entropy)
 from .panoptic_loss import DeeplabPanopticLoss, deeplab_panoptic_loss
@@ -15,4 +16,5 @@ __all__ = ["flow_warp", "mesh_grid", "norm_grid", "photometric_loss", "edge_smoo
            "seg_ohem_cross_entropy", "MixSoftmaxCrossEntropyLoss", "SoftmaxCrossEntropyOHEMLoss", "MixSoftmaxCrossEntropyOHEMLoss",
            "inv_huber_loss", "InvHuberLoss", "InvHuberLossPyr", "ScaleInvariantError", "DepthAwareLoss",
            "rmi_loss", "RMILoss", "RMILossAux", "MultiScaleRMILoss",
-           "deeplab_panoptic_loss", "DeeplabPanopticLoss"]
+           "deeplab_panoptic_loss", "DeeplabPanopticLoss",
+           "DetrLoss", "detr_set_loss"]

@@ -626,6 +626,56 @@ int cerberus_ocr_attention_backward(const void *grad_context, const void *query,
                                     void *grad_query, void *grad_key, void *grad_value, void *dsim, void *workspace,
                                     int64_t workspace_bytes, int B, int C, int R, int HW, float scale, int dtype, void *stream);
 
+/* The DETR set criterion (additions only: no ABI bump): the Hungarian matcher's cost matrix, the rectangular linear sum assignment
+ * and the matched loss terms of the reference's DetrLoss / HungarianMatcher, for all L decoder layers of a step at once, fp32.
+ *
+ *   logits (N,Q,C1), boxes (N,Q,4) cxcywh, N = L B with the layers stacked layer-major over a batch of B
+ *   tgt_labels (B,Tmax) int64, tgt_boxes (B,Tmax,4) fp32, tgt_count (B,) int32: the targets padded per image of the batch; image n
+ *   reads row n % B; a count is clamped to 0..Tmax; a slot at or past the count is never read into a result
+ *   fused limits: 1 <= Q <= 256, 0 <= Tmax <= 128, Q Tmax <= 16384, 2 <= C1 <= 256: cerberus_detr_fused_ok(Q, Tmax, C1) is 1 inside
+ *
+ * Matching cost of query q and target t:  w_bbox |p - t|_1 - w_class softmax(logits[q])[label t] - w_giou GIoU(xyxy(p), xyxy(t)).
+ *   A non-finite entry becomes 1e9 and sets bit 0 of status[n]; a label outside [0, C1) among the counted targets is costed the
+ *   same way and sets bit 1 (the loss counts a query matched to it as no-object).
+ *   match_cost      : cost (N,Q,Tmax) fp32, padding columns zeroed; status (N,) int32 or null
+ *   lsap            : solves a caller-given (N,Q,Tmax) fp32 matrix (non-finite entries as above); status (N,) int32 or null
+ *   hungarian_match : the matrix is formed in LDS and solved there; bit for bit the result of lsap on match_cost's matrix
+ *   match (N,Q) int32: the target of a query, or -1; min(Q, count) queries are matched, every target at most once.  The solver is
+ *   the shortest-augmenting-path algorithm (Jonker-Volgenant, rectangular after Crouse), one wavefront per image with float64 duals:
+ *   optimal for the fp32 matrix as given; the lowest column index wins a tie.  Every loop has a trip count fixed by Q and the count.
+ *
+ * Set loss, per layer l:  losses (L,4) fp32 = [loss_ce, loss_bbox, loss_giou, cardinality_error]
+ *   loss_ce = sum w[c_q] nll_q / sum w[c_q] over the B Q queries of the layer, c_q = tgt_labels[match] or the no-object class C1 - 1,
+ *   weight (C1,) fp32;  loss_bbox = sum over matched |p - t|_1 / num_boxes;  loss_giou = sum over matched (1 - GIoU) / num_boxes;
+ *   cardinality_error = mean_b |#{q: argmax != C1 - 1} - count_b|.  num_boxes: ONE float in device memory.  A match outside
+ *   [0, count) counts as unmatched.  wsum (L,) float64 = sum w[c_q], kept for the backward.
+ *   One workgroup per image writes float64 partial sums, one workgroup adds them in index order: no floating-point atomics.
+ *   workspace : cerberus_detr_workspace_bytes(N) bytes, 8-byte aligned, fully overwritten.
+ *   backward  : grad_losses (L,4) fp32 -> grad_logits (N,Q,C1), grad_boxes (N,Q,4), every element written in one launch; unmatched
+ *   queries get zeros in grad_boxes; the cardinality column carries no gradient.
+ * Box rows are read with 16-byte loads where the base pointer allows and with scalar loads otherwise: no alignment beyond the
+ * element's is required.  No host synchronisation: capturable.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; N < 0, B or Q <= 0, C1 < 2, Tmax < 0, N % B != 0
+ * CERB_EINVAL; a size past the fused limits CERB_EUNSUPPORTED; then N == 0 returns 0 without a launch; a null pointer (the targets
+ * and the matrix may be null when Tmax == 0), a workspace that is misaligned or too small CERB_EINVAL -- all before any launch. */
+int cerberus_detr_fused_ok(int Q, int Tmax, int C1);
+int64_t cerberus_detr_workspace_bytes(int N);
+int cerberus_detr_match_cost(const void *logits, const void *boxes, const void *tgt_labels, const void *tgt_boxes, const void *tgt_count,
+                             void *cost, void *status, int N, int B, int Q, int C1, int Tmax, float w_class, float w_bbox,
+                             float w_giou, int dtype, void *stream);
+int cerberus_detr_lsap(const void *cost, const void *tgt_count, void *match, void *status, int N, int B, int Q, int Tmax, void *stream);
+int cerberus_detr_hungarian_match(const void *logits, const void *boxes, const void *tgt_labels, const void *tgt_boxes,
+                                  const void *tgt_count, void *match, void *status, int N, int B, int Q, int C1, int Tmax,
+                                  float w_class, float w_bbox, float w_giou, int dtype, void *stream);
+int cerberus_detr_set_loss_forward(const void *logits, const void *boxes, const void *match, const void *tgt_labels,
+                                   const void *tgt_boxes, const void *tgt_count, const void *weight, const void *num_boxes, void *losses,
+                                   void *wsum, void *workspace, int64_t workspace_bytes, int N, int B, int Q, int C1, int Tmax,
+                                   int dtype, void *stream);
+int cerberus_detr_set_loss_backward(const void *logits, const void *boxes, const void *match, const void *tgt_labels,
+                                    const void *tgt_boxes, const void *tgt_count, const void *weight, const void *num_boxes,
+                                    const void *wsum, const void *grad_losses, void *grad_logits, void *grad_boxes, int N, int B, int Q,
+                                    int C1, int Tmax, int dtype, void *stream);
+
 /* The device side of the panoptic metric (additions only: no ABI bump): what the reference's PanopticMetric
  * (nnet_training/statistics/panoptic.py) and utilities/panoptic_post_processing.py do to the centre heat map, the offset map and
  * the id / class maps of every image.  Forward only, no host synchronisation, no floating-point atomics: capturable and
