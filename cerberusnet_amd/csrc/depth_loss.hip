@@ -101,22 +101,6 @@ __device__ __forceinline__ float pixel_grad(float p, float g, float c, float m, 
 // ---- folds of non-negative floats as unsigned integers -----------------------------------------------------------------
 __device__ __forceinline__ unsigned err_bits(float err) { return __float_as_uint(err); }   // err >= 0 or a positive NaN
 
-__device__ __forceinline__ unsigned block_max_bits(unsigned v, unsigned *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o, 64)));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return max(max(red[0], red[1]), max(red[2], red[3]));
-}
-
-__device__ __forceinline__ unsigned block_sum_count(unsigned v, unsigned *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // the maximum of the max pass's partials, in every thread
 __device__ __forceinline__ unsigned fold_parts(const unsigned *__restrict__ pmax, int nparts, unsigned *red) {
     unsigned v = 0u;
@@ -127,7 +111,7 @@ __device__ __forceinline__ unsigned fold_parts(const unsigned *__restrict__ pmax
     } else {
         for (int i = i0; i < nparts; ++i) v = max(v, pmax[i]);
     }
-    return block_max_bits(v, red);
+    return block_max(v, red);
 }
 
 // ---- forward, pass 1: the maximum ------------------------------------------------------------------------------------
@@ -153,7 +137,7 @@ __global__ __launch_bounds__(kThreads) void inv_huber_max_kernel(const float *__
             }
         }
     }
-    const unsigned t = block_max_bits(v, red);
+    const unsigned t = block_max(v, red);
     if (threadIdx.x == 0) pmax[blockIdx.x] = t;
 }
 
@@ -205,9 +189,9 @@ __global__ __launch_bounds__(kThreads) void inv_huber_sum_kernel(const float *__
             s4[k] = stage[kChunk + threadIdx.x * kQuad + k];
         }
     }
-    const float a = ((t4[0] + t4[1]) + t4[2]) + t4[3], s = ((s4[0] + s4[1]) + s4[2]) + s4[3];
+    const float a = quad_sum(t4), s = quad_sum(s4);
     const float ta = block_sum(a, red_a), ts = block_sum(s, red_s);
-    const unsigned tt = block_sum_count(ties, red_t);
+    const unsigned tt = block_sum(ties, red_t);
     if (threadIdx.x == 0) {
         psum[blockIdx.x] = ta;
         ps[blockIdx.x] = ts;
@@ -235,15 +219,7 @@ __global__ __launch_bounds__(kThreads) void inv_huber_final_kernel(const unsigne
     red[0][threadIdx.x] = a;
     red[1][threadIdx.x] = b;
     red_t[threadIdx.x] = t;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-            red_t[threadIdx.x] += red_t[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    tree_sum(red, red_t);
     if (threadIdx.x == 0) {
         const float c = 0.2f * m, count = static_cast<float>(N);
         const bool flat = c == 0.f;                  // no valid pixel, or every valid pixel exact: the limit, not 0 / 0

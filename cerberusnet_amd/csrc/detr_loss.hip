@@ -6,6 +6,7 @@
 //   logits (N,Q,C1), boxes (N,Q,4) cxcywh, N = L B layer-major; tgt_labels (B,Tmax) int64, tgt_boxes (B,Tmax,4), tgt_count (B,) int32;
 //   image n reads target row n % B; a slot at or past tgt_count[b] is never read into a result.
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace cerb {
 namespace {
@@ -15,7 +16,7 @@ constexpr int kMaxT = 128;            // targets per image
 constexpr int kMaxQT = 16384;         // Q * Tmax: a 64 KiB fp32 cost matrix in LDS
 constexpr int kMaxC = 256;            // classes, the no-object class included
 constexpr int kSlots = 4;             // columns per lane: kMaxQ / 64
-constexpr int kThreads = 256;         // the loss kernels: one thread per query
+constexpr int kThreads = kReduceThreads;   // the loss kernels: one thread per query
 constexpr int kTerms = 5;             // per-image partial sums of the forward: w nll, w, L1, 1 - GIoU, #{argmax != no-object}
 constexpr float kBigCost = 1.0e9f;    // what a non-finite cost entry becomes (status bit 0)
 constexpr int kStatusNonFinite = 1;
@@ -369,12 +370,6 @@ __global__ __launch_bounds__(kThreads) void detr_match_cost_kernel(const float *
 }
 
 // ---- the set loss ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // the class a query is trained to and its matched target (or -1): a match outside [0, T) counts as unmatched, a label outside
 // [0, C1) as no-object
 __device__ __forceinline__ int target_of(const int *match_row, int q, int T) {
@@ -426,14 +421,11 @@ __global__ __launch_bounds__(kThreads) void detr_loss_fwd_kernel(const float *__
     }
 #pragma unroll
     for (int k = 0; k < kTerms; ++k) {
-        const double v = wave_sum_d(acc[k]);
+        const double v = wave_sum(acc[k]);
         if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v;
     }
     __syncthreads();
-    if (threadIdx.x < kTerms) {
-        const int k = threadIdx.x;
-        part[static_cast<size_t>(n) * kTerms + k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    }
+    if (threadIdx.x < kTerms) part[static_cast<size_t>(n) * kTerms + threadIdx.x] = waves_fold<FoldSum>(red[threadIdx.x]);
 }
 
 // the fixed-order finish: one workgroup, layer l adds its B images in index order

@@ -73,20 +73,9 @@ __device__ __forceinline__ void load_quad_labels(const int64_t *__restrict__ t, 
     }
 }
 
-// ---- float64 folds in a fixed order ----------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned wave_count(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o, 64));
-    return v;
-}
-
-// the workgroup's partials of NS sums and NC counts, left at slot `slot` of the workspace by thread 0
+// ---- float64 folds in a fixed order (loss_reduce.h) ------------------------------------------------------------------------
+// the workgroup's partials of NS sums and NC counts, left at slot `slot` of the workspace by thread 0: block_sum's pieces,
+// with one barrier for all of them
 template <int NS, int NC>
 __device__ __forceinline__ void leave_partials(const double (&s)[NS], const unsigned *c, double *__restrict__ psum,
                                                unsigned *__restrict__ pcnt, int64_t slot) {
@@ -95,20 +84,20 @@ __device__ __forceinline__ void leave_partials(const double (&s)[NS], const unsi
     const int wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-        const double v = wave_sum64(s[i]);
+        const double v = wave_sum(s[i]);
         if ((threadIdx.x & 63) == 0) red_s[i][wave] = v;
     }
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
-        const unsigned v = wave_count(c[i]);
+        const unsigned v = wave_sum(c[i]);
         if ((threadIdx.x & 63) == 0) red_c[i][wave] = v;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 0; i < NS; ++i) psum[slot * NS + i] = (red_s[i][0] + red_s[i][1]) + (red_s[i][2] + red_s[i][3]);
+        for (int i = 0; i < NS; ++i) psum[slot * NS + i] = waves_fold<FoldSum>(red_s[i]);
 #pragma unroll
-        for (int i = 0; i < NC; ++i) pcnt[slot * NC + i] = (red_c[i][0] + red_c[i][1]) + (red_c[i][2] + red_c[i][3]);
+        for (int i = 0; i < NC; ++i) pcnt[slot * NC + i] = waves_fold<FoldSum>(red_c[i]);
     }
 }
 
@@ -136,16 +125,10 @@ __global__ __launch_bounds__(kThreads) void metric_finish_kernel(const double *_
     for (int i = 0; i < NS; ++i) red_s[i][threadIdx.x] = s[i];
 #pragma unroll
     for (int i = 0; i < NC; ++i) red_c[i][threadIdx.x] = c[i];
-    __syncthreads();
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        if (static_cast<int>(threadIdx.x) < h) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i) red_s[i][threadIdx.x] += red_s[i][threadIdx.x + h];
-#pragma unroll
-            for (int i = 0; i < NC; ++i) red_c[i][threadIdx.x] += red_c[i][threadIdx.x + h];
-        }
-        __syncthreads();
-    }
+    if constexpr (NC > 0)
+        tree_sum(red_s, red_c);
+    else
+        tree_sum(red_s);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int i = 0; i < NS; ++i) sums[static_cast<int64_t>(blockIdx.x) * NS + i] = red_s[i][0];

@@ -22,11 +22,12 @@
 #include <math.h>
 
 #include "common.h"
+#include "loss_reduce.h"
 
 namespace cerb {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kReduceThreads;
 constexpr int kMaxRegions = 32;
 constexpr int kChunk = 256;                  // P: pixels per pooling workgroup, and per workgroup of the lane-per-pixel kernels
 constexpr int kPoolTile = 32;                // channels per LDS tile of the pooling kernel
@@ -66,11 +67,7 @@ __global__ __launch_bounds__(kThreads) void ocr_row_stats_kernel(const float *__
             if (HW - (q << 2) > j) m = fmaxf(m, scale * v[j]);
     }
     red[tid] = m;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
-        __syncthreads();
-    }
+    tree_fold<FoldMax>(red);
     m = red[0];
     __syncthreads();
     float sum = 0.f;
@@ -82,11 +79,7 @@ __global__ __launch_bounds__(kThreads) void ocr_row_stats_kernel(const float *__
             if (HW - (q << 2) > j) sum += expf(scale * v[j] - m);
     }
     red[tid] = sum;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
+    tree_sum(red);
     if (tid == 0) {
         stats[2 * static_cast<size_t>(blockIdx.x)] = m;
         stats[2 * static_cast<size_t>(blockIdx.x) + 1] = 1.f / red[0];
@@ -184,8 +177,7 @@ __global__ __launch_bounds__(64) void ocr_dot_kernel(const float *__restrict__ g
         const size_t i = (static_cast<size_t>(b) * C + c) * R + k;
         acc = fmaf(g[i], ctx[i], acc);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) dot[blockIdx.x] = acc;
 }
 

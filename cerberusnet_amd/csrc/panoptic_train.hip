@@ -104,18 +104,12 @@ __device__ __forceinline__ int find_row(const int64_t *table, int count, int64_t
     return -1;
 }
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += static_cast<u64>(__shfl_xor(static_cast<long long>(v), o, 64));
-    return v;
-}
-
 // adds (n, sy, sx) of `row` (-1: nothing) to the workgroup's LDS bins; called by whole waves
 __device__ __forceinline__ void add_moments(u64 *bins, int row, unsigned n, u64 sy, u64 sx) {
     const int r0 = __shfl(row, 0, 64);
     if (__all(row == r0)) {          // the usual case: the wave's pixels lie in one segment
         if (r0 < 0) return;
-        const u64 tn = wave_sum_u64(n), ty = wave_sum_u64(sy), tx = wave_sum_u64(sx);
+        const u64 tn = wave_sum<u64>(n), ty = wave_sum(sy), tx = wave_sum(sx);
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(&bins[r0], tn);
             atomicAdd(&bins[kMaxSegments + r0], ty);
@@ -409,7 +403,7 @@ __global__ __launch_bounds__(kThreads) void ploss_partial_kernel(Term t, float *
             m4[k] = stage[2 * kChunk + threadIdx.x * kQuad + k];
         }
     }
-    const float f = ((f4[0] + f4[1]) + f4[2]) + f4[3], g = ((g4[0] + g4[1]) + g4[2]) + g4[3], m = ((m4[0] + m4[1]) + m4[2]) + m4[3];
+    const float f = quad_sum(f4), g = quad_sum(g4), m = quad_sum(m4);
     const float tf = block_sum(f, red[0]), tg = block_sum(g, red[1]), tm = block_sum(m, red[2]);
     if (threadIdx.x == 0) {
         pf[blockIdx.x] = tf;
@@ -447,14 +441,7 @@ __global__ __launch_bounds__(kThreads) void ploss_final_kernel(const float *__re
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = acc[k];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    tree_sum(red);
     if (threadIdx.x == 0) {
         float vc, sc, vo, so;
         term_value(red[0][0], red[1][0], red[2][0], c_masked != 0, n_c, cw, mode, vc, sc);

@@ -28,13 +28,14 @@
 // Labels never form an address.  An ignored pixel is skipped by selection: a NaN logit there changes nothing and its
 // gradient is 0.0f.
 #include "common.h"
+#include "loss_reduce.h"
 
 #pragma clang fp contract(off)
 
 namespace cerb {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kReduceThreads;
 constexpr int kClassGroup = 8;        // class planes per workgroup of the front end and the backward
 constexpr int kMaxPool = 8;
 constexpr int kR = 3, kD = kR * kR;   // radius, and the dimension of a point
@@ -67,19 +68,11 @@ inline Geom make_geom(int N, int C, int H, int W, int p) {
     return g;
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the workgroup's 4 waves in wave order (every thread returns the same value); red: 4 doubles
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    v = wave_sum(v);
-    __syncthreads();                 // red may still be read from the call before
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+// loss_reduce.h's block_sum behind a barrier of its own: consecutive calls here share one red[4], which may still be read from
+// the call before
+__device__ __forceinline__ double block_sum_reusing(double v, double *red) {
     __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
+    return block_sum(v, red);
 }
 
 // ---- what the front end and the backward share -------------------------------------------------------------------
@@ -196,8 +189,8 @@ __global__ __launch_bounds__(kThreads) void rmi_front_kernel(const float *__rest
             la[o] = static_cast<float>(hits) / div;
         }
     }
-    const double tb = block_sum(static_cast<double>(bacc), red);
-    const double tc = block_sum(static_cast<double>(count), red);
+    const double tb = block_sum_reusing(static_cast<double>(bacc), red);
+    const double tc = block_sum_reusing(static_cast<double>(count), red);
     if (threadIdx.x == 0) {
         const int64_t part = (static_cast<int64_t>(n) * g.ncg + blockIdx.y) * g.nblk + blockIdx.x;
         pbce[part] = tb;
@@ -216,14 +209,7 @@ __global__ __launch_bounds__(kThreads) void rmi_bce_final_kernel(const double *_
     }
     red[0][threadIdx.x] = a;
     red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    tree_sum(red);
     if (threadIdx.x == 0) {
         const double num = red[0][0], valid = red[1][0];
         const float v = static_cast<float>(num / (valid + 1.0));
@@ -261,7 +247,7 @@ __global__ __launch_bounds__(kThreads) void rmi_mean_kernel(const float *__restr
     const double count_pos = static_cast<double>(g.P);
 #pragma unroll
     for (int k = 0; k < kD; ++k) {
-        const double tl = block_sum(sl[k], red), tp = block_sum(sp[k], red);
+        const double tl = block_sum_reusing(sl[k], red), tp = block_sum_reusing(sp[k], red);
         if (threadIdx.x == 0) {
             means[static_cast<int64_t>(blockIdx.x) * 2 * kD + k] = tl / count_pos;
             means[static_cast<int64_t>(blockIdx.x) * 2 * kD + kD + k] = tp / count_pos;

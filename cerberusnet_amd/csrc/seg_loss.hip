@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void seg_ce_fwd_kernel(const float *__res
             d4[k] = stage[kChunk + threadIdx.x * kQuad + k];
         }
     }
-    const float n = ((n4[0] + n4[1]) + n4[2]) + n4[3], d = ((d4[0] + d4[1]) + d4[2]) + d4[3];
+    const float n = quad_sum(n4), d = quad_sum(d4);
     const float tn = block_sum(n, red_n), td = block_sum(d, red_d);
     if (threadIdx.x == 0) {
         pnum[blockIdx.x] = tn;
@@ -143,14 +143,7 @@ __global__ __launch_bounds__(kThreads) void seg_ce_final_kernel(const float *__r
     }
     red[0][threadIdx.x] = a;
     red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    tree_sum(red);
     if (threadIdx.x == 0) {
         const float num = red[0][0], den = red[1][0];
         const float ce = num / den;              // 0 / 0 = NaN when nothing counts, as the stock mean

@@ -303,16 +303,13 @@ __global__ __launch_bounds__(kThreads) void ohem_sum_kernel(const float *__restr
             n4[k] = __builtin_nanf("");                     // a label outside [0, C) that is not the ignore value, as seg_loss.hip
         }
     }
-    const float n = ((n4[0] + n4[1]) + n4[2]) + n4[3], d = ((d4[0] + d4[1]) + d4[2]) + d4[3];
+    const float n = quad_sum(n4), d = quad_sum(d4);
     const float tn = block_sum(n, red_n), td = block_sum(d, red_d);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
-    if ((threadIdx.x & 63) == 0) red_k[threadIdx.x >> 6] = kept;
-    __syncthreads();
+    const unsigned tk = block_sum(kept, red_k);
     if (threadIdx.x == 0) {
         pnum[blockIdx.x] = tn;
         pden[blockIdx.x] = td;
-        pkept[blockIdx.x] = (red_k[0] + red_k[1]) + (red_k[2] + red_k[3]);
+        pkept[blockIdx.x] = tk;
     }
 }
 
@@ -333,15 +330,7 @@ __global__ __launch_bounds__(kThreads) void ohem_final_kernel(const float *__res
     red[0][threadIdx.x] = a;
     red[1][threadIdx.x] = b;
     redk[threadIdx.x] = k;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (static_cast<int>(threadIdx.x) < s) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + s];
-            red[1][threadIdx.x] += red[1][threadIdx.x + s];
-            redk[threadIdx.x] += redk[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    tree_sum(red, redk);
     if (threadIdx.x == 0) {
         const float num = red[0][0], den = red[1][0];
         const float ce = num / den;              // 0 / 0 = NaN when nothing is kept, as the stock mean

@@ -3,7 +3,7 @@ that single out one partial, shared by tests/test_reduction_tiers_cpu.py (which 
 the GPU tests of the three ops.  Also the non-finite and far-apart logit patterns of the segmentation loss.
 
 All three files reduce alike: a workgroup folds ``*_CHUNK_PIXELS`` pixels into one partial, and a second launch of ONE
-workgroup of ``FINISH_THREADS`` threads adds the partials by ``for (i = threadIdx.x; i < n; i += 256)`` and an LDS tree.  Up to
+workgroup of ``FINISH_THREADS`` threads adds the partials by ``for (i = threadIdx.x; i < n; i += 256)`` and the LDS tree of loss_reduce.h (``tree_sum``).  Up to
 256 partials every thread of a finish kernel reads at most one.  The constants the kernels do not export are restated here
 with the line they mirror."""
 import functools
