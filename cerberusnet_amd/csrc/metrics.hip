@@ -272,40 +272,14 @@ __global__ __launch_bounds__(kThreads) void flow_metric_kernel(const float *__re
 
 // ---- (d) the warp's sum of absolute differences -------------------------------------------------------------------------------
 // One pixel's bilinear sample of flow_warp's default modes (border padding, the quirk-Q2 normalisation of warp_common.h):
-// positions, weights and the order of the four products are those of warp_fwd_kernel, so that a sample equals the element
-// flow_warp would have written.
-struct Taps {
-    float wnw, wne, wsw, wse;
-    int o00;                       // offset of the north-west tap in a plane (only used where a tap is inside)
-    bool nw, ne, sw, se;           // the tap lies inside the image
-};
-
-__device__ __forceinline__ Taps taps_of(int x, int y, float fx, float fy, int H, int W) {
-    const float cx = source_coord<float>(x, fx, W, CERB_PAD_BORDER).pos, cy = source_coord<float>(y, fy, H, CERB_PAD_BORDER).pos;
-    const float x0f = floorf(cx), y0f = floorf(cy);
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    Taps t;
-    t.wnw = (x1f - cx) * (y1f - cy);
-    t.wne = (cx - x0f) * (y1f - cy);
-    t.wsw = (x1f - cx) * (cy - y0f);
-    t.wse = (cx - x0f) * (cy - y0f);
-    const int x0 = tap_index(x0f), y0 = tap_index(y0f);
-    const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-    t.nw = oky0 && okx0; t.ne = oky0 && okx1; t.sw = oky1 && okx0; t.se = oky1 && okx1;
-    t.o00 = (t.nw || t.ne || t.sw || t.se) ? y0 * W + x0 : 0;
-    return t;
-}
-
-__device__ __forceinline__ float sample(const float *__restrict__ plane, const Taps &t, int W) {
-    const float *q = plane + t.o00;
+// the position is source_coord's, the weights, flags and the order of the four products are Bilinear's (warp_common.h), so
+// that a sample equals the element flow_warp would have written.
+__device__ __forceinline__ float sample(const float *__restrict__ plane, const Bilinear<float> &t, int H, int W) {
+    const float *q = plane + (t.dead(H, W) ? 0 : t.y0() * W + t.x0());     // the north-west tap (only used where a tap is inside)
     // a tap outside the image is never addressed and counts as an exact zero
-    const float vnw = t.nw ? q[0] : 0.f, vne = t.ne ? q[1] : 0.f, vsw = t.sw ? q[W] : 0.f, vse = t.se ? q[W + 1] : 0.f;
-    float acc = vnw * t.wnw;
-    acc += vne * t.wne;
-    acc += vsw * t.wsw;
-    acc += vse * t.wse;
-    return acc;
+    bool nw, ne, sw, se;
+    t.inside(H, W, nw, ne, sw, se);
+    return t.blend(nw ? q[0] : 0.f, ne ? q[1] : 0.f, sw ? q[W] : 0.f, se ? q[W + 1] : 0.f);
 }
 
 template <bool kVec>
@@ -319,14 +293,15 @@ __global__ __launch_bounds__(kThreads) void warp_sad_kernel(const float *__restr
     float fx[kQuad], fy[kQuad];
     load_quad<kVec>(fl, p0, hw, 0.f, fx);
     load_quad<kVec>(fl + hw, p0, hw, 0.f, fy);
-    Taps taps[kQuad];
+    Bilinear<float> taps[kQuad];
     const int y0 = p0 / W, x0 = p0 - y0 * W;
 #pragma unroll
     for (int k = 0; k < kQuad; ++k) {
         int x = x0 + k, y = y0;                  // a lane's 4 pixels may cross a row (more than once when W < 4)
         while (x >= W) { x -= W; ++y; }
         const bool in = p0 + k < hw;
-        taps[k] = taps_of(in ? x : 0, in ? y : 0, fx[k], fy[k], H, W);
+        taps[k] = Bilinear<float>(source_coord<float>(in ? x : 0, fx[k], W, CERB_PAD_BORDER).pos,
+                                  source_coord<float>(in ? y : 0, fy[k], H, CERB_PAD_BORDER).pos);
     }
     double acc[kQuad] = {0.0, 0.0, 0.0, 0.0};
     for (int c = 0; c < C; ++c) {
@@ -335,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void warp_sad_kernel(const float *__restr
         load_quad<kVec>(img + o, p0, hw, 0.f, v);
 #pragma unroll
         for (int k = 0; k < kQuad; ++k) {
-            const float term = fabsf(v[k] - sample(src + o, taps[k], W));
+            const float term = fabsf(v[k] - sample(src + o, taps[k], H, W));
             acc[k] += p0 + k < hw ? static_cast<double>(term) : 0.0;
         }
     }

@@ -37,7 +37,7 @@
 //
 // ---- occlusion_mask_bidirection -------------------------------------------------------------------------------------
 // One launch, one thread per pixel: the two planes of flow21 are sampled where flow_warp(., flow12, pad='zeros') samples
-// them -- source_coord / tap_index / tap_ptr of warp_common.h and warp_fwd_kernel's weights and summation order, so the
+// them -- source_coord, Bilinear (weights, flags, summation order, clamped offsets) and tap_ptr of warp_common.h, so the
 // sampled values w are the bits flow_warp returns, quirk Q2 (normalised by W - 1, sampled with align_corners=False)
 // included -- then, each step rounded on its own as the reference's separate launches do (contraction is off),
 //     |f12 + w|^2 > scale (|f12|^2 + |w|^2) + bias   ->  1.0, else 0.0.
@@ -155,34 +155,18 @@ __global__ __launch_bounds__(kThreads) void occ_bidirection_kernel(const float *
     const int y = static_cast<int>(p / W), x = static_cast<int>(p - static_cast<int64_t>(y) * W);
     const float *fl = flow12 + b * 2 * plane + p;
     const float fx = fl[0], fy = fl[plane];
-    // warp_fwd_kernel, bilinear, pad = zeros, on the two channels of flow21
-    const Coord<float> cx = source_coord<float>(x, fx, W, CERB_PAD_ZEROS);
-    const Coord<float> cy = source_coord<float>(y, fy, H, CERB_PAD_ZEROS);
-    const float x0f = floorf(cx.pos), y0f = floorf(cy.pos);
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    const float wnw = (x1f - cx.pos) * (y1f - cy.pos);
-    const float wne = (cx.pos - x0f) * (y1f - cy.pos);
-    const float wsw = (x1f - cx.pos) * (cy.pos - y0f);
-    const float wse = (cx.pos - x0f) * (cy.pos - y0f);
-    const int x0 = tap_index(x0f), y0 = tap_index(y0f);
-    const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-    // an offset is formed only from taps inside the map; absent taps read a block of zeros (tap_ptr)
-    const int cx0 = min(max(x0, 0), W - 1), cy0 = min(max(y0, 0), H - 1);
+    // flow_warp's bilinear sample (warp_common.h: Bilinear), pad = zeros, on the two channels of flow21
+    const Bilinear<float> t(source_coord<float>(x, fx, W, CERB_PAD_ZEROS).pos, source_coord<float>(y, fy, H, CERB_PAD_ZEROS).pos);
+    int64_t onw, one, osw, ose;
+    t.clamped_offsets(H, W, onw, one, osw, ose);
+    bool nw, ne, sw, se;
+    t.inside(H, W, nw, ne, sw, se);
     const float *img = flow21 + b * 2 * plane;
     float w[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const float *ch = img + c * plane;
-        const float v0 = ld(tap_ptr(ch + static_cast<int64_t>(cy0) * W + cx0, oky0 && okx0));
-        const float v1 = ld(tap_ptr(ch + static_cast<int64_t>(cy0) * W + min(x0 + 1, W - 1), oky0 && okx1));
-        const float v2 = ld(tap_ptr(ch + static_cast<int64_t>(min(y0 + 1, H - 1)) * W + cx0, oky1 && okx0));
-        const float v3 = ld(tap_ptr(ch + static_cast<int64_t>(min(y0 + 1, H - 1)) * W + min(x0 + 1, W - 1), oky1 && okx1));
-        float a = v0 * wnw;
-        a += v1 * wne;
-        a += v2 * wsw;
-        a += v3 * wse;
-        w[c] = a;
+        w[c] = t.blend(ld(tap_ptr(ch + onw, nw)), ld(tap_ptr(ch + one, ne)), ld(tap_ptr(ch + osw, sw)), ld(tap_ptr(ch + ose, se)));
     }
     // :101-105, one rounding per stock launch
     const float dx = fx + w[0], dy = fy + w[1];

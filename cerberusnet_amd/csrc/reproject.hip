@@ -18,7 +18,8 @@
 //     g   = (px / (W - 1) - 0.5) * 2                   quirk Q2: normalised by W - 1 ...
 //     s   = ((g + 1) * W - 1) / 2                      ... un-normalised with align_corners=False (ATen's fused multiply-add)
 //     s   = clip(s, 0, W - 1)                          padding_mode="border"
-// then flow_warp's bilinear taps, weights and summation order (warp_common.h: tap_index, tap_ptr, clip_kills_grad).
+// then flow_warp's bilinear taps, weights and summation order (warp_common.h: Bilinear, tap_ptr, flow_grad_terms,
+// clip_kills_grad).
 //
 // Backward: one thread per pixel recomputes the position and gathers -- no atomics, no workspace, every element of
 // grad_depth written exactly once:
@@ -87,29 +88,6 @@ __device__ __forceinline__ Coord<float> sample_coord(float pix, int size) {
     return {p, m};
 }
 
-struct Taps {
-    float ax, bx, ay, by;                // x1 - sx, sx - x0, y1 - sy, sy - y0
-    int64_t onw, one, osw, ose;          // offsets inside a plane, clamped into it
-    bool nw, ne, sw, se;                 // the tap is inside the image
-};
-
-__device__ __forceinline__ Taps make_taps(float sx, float sy, int H, int W) {
-    Taps t;
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-    t.ax = x1f - sx; t.bx = sx - x0f;
-    t.ay = y1f - sy; t.by = sy - y0f;
-    const int x0 = tap_index(x0f), y0 = tap_index(y0f);
-    const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-    const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-    // an offset is formed only from coordinates inside the image; absent taps read a block of zeros (tap_ptr)
-    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x0 + 1, 0), W - 1);
-    const int64_t r0 = static_cast<int64_t>(min(max(y0, 0), H - 1)) * W, r1 = static_cast<int64_t>(min(max(y0 + 1, 0), H - 1)) * W;
-    t.onw = r0 + cx0; t.one = r0 + cx1; t.osw = r1 + cx0; t.ose = r1 + cx1;
-    t.nw = oky0 && okx0; t.ne = oky0 && okx1; t.sw = oky1 && okx0; t.se = oky1 && okx1;
-    return t;
-}
-
 // the work item of a wavefront: (item b, row y, 64-pixel segment); false when there is none
 __device__ __forceinline__ bool wave_item(int items, int segs, int H, int &b, int &y, int &x) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kPix), lane = threadIdx.x & (kPix - 1);
@@ -132,19 +110,16 @@ __global__ __launch_bounds__(kThreads) void reproject_warp_fwd_kernel(const floa
     const Ray r = project(inv_k + b * 9, proj + b * 12, static_cast<float>(x), static_cast<float>(y), depth[b * plane + p], eps);
     const Coord<float> cx = sample_coord(r.px / r.d, W);
     const Coord<float> cy = sample_coord(r.py / r.d, H);
-    const Taps t = make_taps(cx.pos, cy.pos, H, W);
-    const float wnw = t.ax * t.ay, wne = t.bx * t.ay, wsw = t.ax * t.by, wse = t.bx * t.by;
+    const Bilinear<float> t(cx.pos, cy.pos);
+    int64_t onw, one, osw, ose;
+    t.clamped_offsets(H, W, onw, one, osw, ose);
+    bool nw, ne, sw, se;
+    t.inside(H, W, nw, ne, sw, se);
     const float *img = image + static_cast<int64_t>(b) * C * plane;
     float *dst = out + static_cast<int64_t>(b) * C * plane + p;
     for (int c = 0; c < C; ++c) {
         const float *ch = img + c * plane;
-        const float vnw = ld(tap_ptr(ch + t.onw, t.nw)), vne = ld(tap_ptr(ch + t.one, t.ne));
-        const float vsw = ld(tap_ptr(ch + t.osw, t.sw)), vse = ld(tap_ptr(ch + t.ose, t.se));
-        float acc = vnw * wnw;     // absent taps contribute exact zeros
-        acc += vne * wne;
-        acc += vsw * wsw;
-        acc += vse * wse;
-        dst[c * plane] = acc;
+        dst[c * plane] = t.blend(ld(tap_ptr(ch + onw, nw)), ld(tap_ptr(ch + one, ne)), ld(tap_ptr(ch + osw, sw)), ld(tap_ptr(ch + ose, se)));
     }
 }
 
@@ -160,18 +135,23 @@ __global__ __launch_bounds__(kThreads) void reproject_warp_bwd_kernel(const floa
     const Ray r = project(inv_k + b * 9, q, static_cast<float>(x), static_cast<float>(y), depth[b * plane + p], eps);
     const Coord<float> cx = sample_coord(r.px / r.d, W);
     const Coord<float> cy = sample_coord(r.py / r.d, H);
-    const Taps t = make_taps(cx.pos, cy.pos, H, W);
+    const Bilinear<float> t(cx.pos, cy.pos);
+    int64_t onw, one, osw, ose;
+    t.clamped_offsets(H, W, onw, one, osw, ose);
+    bool nw, ne, sw, se;
+    t.inside(H, W, nw, ne, sw, se);
     const float *img = image + static_cast<int64_t>(b) * C * plane;
     const float *go = gout + static_cast<int64_t>(b) * C * plane + p;
     float gix = 0.f, giy = 0.f;       // sum_c grad_out[c] * dv_c/dsx, .. dsy
     for (int c = 0; c < C; ++c) {
         const float *ch = img + c * plane;
         const float g = go[c * plane];
-        const float vnw = ld(tap_ptr(ch + t.onw, t.nw)), vne = ld(tap_ptr(ch + t.one, t.ne));
-        const float vsw = ld(tap_ptr(ch + t.osw, t.sw)), vse = ld(tap_ptr(ch + t.ose, t.se));
-        flow_grad_terms<float>(vnw, vne, vsw, vse, t.ax, t.bx, t.ay, t.by, g, gix, giy);
+        const float vnw = ld(tap_ptr(ch + onw, nw)), vne = ld(tap_ptr(ch + one, ne));
+        const float vsw = ld(tap_ptr(ch + osw, sw)), vse = ld(tap_ptr(ch + ose, se));
+        flow_grad_terms<float>(vnw, vne, vsw, vse, t.ax(), t.bx(), t.ay(), t.by(), g, gix, giy);
     }
-    // autograd's order: grad_grid = mult * sum; through (. - 0.5) * 2: * 2; through / (size - 1)
+    // autograd's order of THIS chain: grad_grid = mult * sum; through (. - 0.5) * 2: * 2; then through / (size - 1).  Not
+    // flow_grad_out: norm_grid divides before it doubles, Project3D doubles last, and the roundings differ.
     const float gpx = cx.mult * gix * 2.0f / static_cast<float>(W - 1);
     const float gpy = cy.mult * giy * 2.0f / static_cast<float>(H - 1);
     // a = proj[:, :3] . u: dp/ddepth

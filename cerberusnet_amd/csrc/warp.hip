@@ -251,7 +251,8 @@ __global__ __launch_bounds__(kPix) void warp_context_kernel(const F *__restrict_
         float *pos = ctx_pos(ctx, B, H, W) + static_cast<int64_t>(b) * 2 * plane + p;
         pos[0] = cx.pos;
         pos[plane] = cy.pos;
-        range.add(x, y, tap_index(floorf(cx.pos)), tap_index(floorf(cy.pos)), W, H);
+        const Bilinear<float> t(cx.pos, cy.pos);
+        range.add(x, y, t.x0(), t.y0(), W, H);
     }
     range.publish(ctx, first, lane);
 }
@@ -299,23 +300,15 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
     const int64_t p = static_cast<int64_t>(blockIdx.x) * kPix + lane;
     const int b = blockIdx.y;
     const bool live = p < plane;
-    A gix = 0, giy = 0;
+    A giy = 0, gix = 0;   // (y first: the compiler pairs the two sums, and this lane order costs two VGPRs fewer -- 72, not 74, in fp32)
     Coord<A> cx{0, 0}, cy{0, 0};
     if (live) {
         const int y = static_cast<int>(p / W), x = static_cast<int>(p % W);
         const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + p;
         cx = source_coord<A>(x, static_cast<A>(ld(fl)), W, pad_mode);
         cy = source_coord<A>(y, static_cast<A>(ld(fl + plane)), H, pad_mode);
-        const A x0f = floor(cx.pos), y0f = floor(cy.pos);
-        const A x1f = x0f + A(1), y1f = y0f + A(1);
-        const A wnw = (x1f - cx.pos) * (y1f - cy.pos);
-        const A wne = (cx.pos - x0f) * (y1f - cy.pos);
-        const A wsw = (x1f - cx.pos) * (cy.pos - y0f);
-        const A wse = (cx.pos - x0f) * (cy.pos - y0f);
-        const int x0 = tap_index(static_cast<float>(x0f)), y0 = tap_index(static_cast<float>(y0f));
-        const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-        const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-        const int64_t o00 = static_cast<int64_t>(y0) * W + x0;
+        const Bilinear<A> t(cx.pos, cy.pos);
+        const int64_t o00 = static_cast<int64_t>(t.y0()) * W + t.x0();
         const int64_t base = static_cast<int64_t>(b) * C * plane;
         if (interp == CERB_INTERP_NEAREST) {
             // grad_image: gradOutput added to the nearbyint tap (ATen's scatter); grad_flow: zero, stored below
@@ -326,6 +319,8 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
                 for (int c = cg; c < C; c += kCg) atomic_accumulate(gimage + q + c * plane, ld(gout + base + c * plane + p));
             }
         }
+        bool nw, ne, sw, se;
+        t.inside(H, W, nw, ne, sw, se);
         // kU channels per trip: all loads of a trip are issued before any is consumed
         constexpr int kU = 4;
         for (int c = cg; c < C && interp != CERB_INTERP_NEAREST; c += kU * kCg) {
@@ -338,8 +333,8 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
                 g[u] = ld(tap_ptr(gout + base + (on ? cc : c) * plane + p, on));
                 vnw[u] = vne[u] = vsw[u] = vse[u] = A(0);
                 if (gflow) {  // kernel-uniform
-                    load_taps<PAIR, T, A>(image + q, oky0 && okx0, oky0 && okx1, vnw[u], vne[u]);
-                    load_taps<PAIR, T, A>(image + q + W, oky1 && okx0, oky1 && okx1, vsw[u], vse[u]);
+                    load_taps<PAIR, T, A>(image + q, nw, ne, vnw[u], vne[u]);
+                    load_taps<PAIR, T, A>(image + q + W, sw, se, vsw[u], vse[u]);
                 }
             }
 #pragma unroll
@@ -348,15 +343,12 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
                 if (cc >= C) break;
                 if (gimage) {
                     const int64_t q = base + cc * plane + o00;
-                    if (oky0 && okx0) atomic_accumulate(gimage + q, wnw * g[u]);
-                    if (oky0 && okx1) atomic_accumulate(gimage + q + 1, wne * g[u]);
-                    if (oky1 && okx0) atomic_accumulate(gimage + q + W, wsw * g[u]);
-                    if (oky1 && okx1) atomic_accumulate(gimage + q + W + 1, wse * g[u]);
+                    if (nw) atomic_accumulate(gimage + q, t.wnw() * g[u]);
+                    if (ne) atomic_accumulate(gimage + q + 1, t.wne() * g[u]);
+                    if (sw) atomic_accumulate(gimage + q + W, t.wsw() * g[u]);
+                    if (se) atomic_accumulate(gimage + q + W + 1, t.wse() * g[u]);
                 }
-                if (gflow) {
-                    flow_grad_terms<A>(vnw[u], vne[u], vsw[u], vse[u], x1f - cx.pos, cx.pos - x0f, y1f - cy.pos,
-                                       cy.pos - y0f, g[u], gix, giy);
-                }
+                if (gflow) flow_grad_terms<A>(vnw[u], vne[u], vsw[u], vse[u], t.ax(), t.bx(), t.ay(), t.by(), g[u], gix, giy);
             }
         }
     }
@@ -368,11 +360,10 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
         A sx = 0, sy = 0;
 #pragma unroll
         for (int k = 0; k < kCg; ++k) { sx += part[k][0][lane]; sy += part[k][1][lane]; }
-        // autograd order: grad_grid = mult * sum ; through norm_grid: / (size-1) then * 2.0
         F *gf = gflow + static_cast<int64_t>(b) * 2 * plane + p;
         const bool nearest = interp == CERB_INTERP_NEAREST;   // no gradient by the position: exact zeros
-        st(gf, nearest ? A(0) : cx.mult * sx / static_cast<A>(W - 1) * A(2.0));
-        st(gf + plane, nearest ? A(0) : cy.mult * sy / static_cast<A>(H - 1) * A(2.0));
+        st(gf, nearest ? A(0) : flow_grad_out(cx.mult, sx, W));
+        st(gf + plane, nearest ? A(0) : flow_grad_out(cy.mult, sy, H));
     }
 }
 
@@ -398,8 +389,9 @@ __global__ __launch_bounds__(kPix * kCg) void warp_bwd_kernel(
 // px per px, the 64 taps of one gather instruction then spread over up to 13 image rows, and the texture path walks
 // every cache line they touch (ablation, same launch: taps redirected to the lane's own pixel 13.5 / 15.5 us; no taps
 // 12.6 / 14.0; no stores 27.7; one or four pixels per lane: the same).
-// Same arithmetic in the same order as warp_fwd_kernel / warp_bwd_kernel (the backward adds its per-channel terms
-// in the four-group order of warp_bwd_kernel<.., 4>): bit-identical results (test).
+// Taps, weights and the order of the sum from Bilinear, the terms from flow_grad_terms / flow_grad_out, as in warp_fwd_kernel
+// / warp_bwd_kernel (the backward adds its per-channel terms in the four-group order of warp_bwd_kernel<.., 4>):
+// bit-identical results (test).
 // Work items in row-major order, XCD-contiguous (an XCD's L2 sees whole image rows and their vertical neighbours).
 template <typename T, typename F, int NC, int PX, bool BWD>
 __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ image, const F *__restrict__ flow,
@@ -443,22 +435,19 @@ __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ im
         }
     }
     float v[PX][NC][4], ax[PX], bx[PX], ay[PX], by[PX], mx[PX], my[PX];
+    Bilinear<float> t[PX];
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
         const Coord<float> cx = source_coord<float>(xs[i], fx[i], W, pad_mode);
         const Coord<float> cy = source_coord<float>(y, fy[i], H, pad_mode);
-        const float x0f = floorf(cx.pos), y0f = floorf(cy.pos);
-        const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-        ax[i] = x1f - cx.pos; bx[i] = cx.pos - x0f;
-        ay[i] = y1f - cy.pos; by[i] = cy.pos - y0f;
+        t[i] = Bilinear<float>(cx.pos, cy.pos);
+        // The fractions are formed HERE, under the loads in flight, and kept: both directions use these values (the forward's
+        // t[i].blend folds onto them).  Asked for after the loads instead, the backward's four pixels' fractions are packed into
+        // v_pk ops with 35 more moves, and the 16-bit form loses a wave per SIMD (96 VGPRs).
+        ax[i] = t[i].ax(); bx[i] = t[i].bx(); ay[i] = t[i].ay(); by[i] = t[i].by();
         mx[i] = cx.mult; my[i] = cy.mult;
-        const int x0 = tap_index(x0f), y0 = tap_index(y0f);
-        const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-        const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-        // |x0|, |y0| <= 2^24: the product may wrap (unsigned arithmetic: defined), but only in-image taps use it
-        const int o00 = static_cast<int>((static_cast<unsigned>(y0) * static_cast<unsigned>(W) + static_cast<unsigned>(x0)) * esz);
-        const int onw = (oky0 && okx0) ? o00 : kDeadOffset, one = (oky0 && okx1) ? o00 + esz : kDeadOffset;
-        const int osw = (oky1 && okx0) ? o00 + W * esz : kDeadOffset, ose = (oky1 && okx1) ? o00 + (W + 1) * esz : kDeadOffset;
+        int onw, one, osw, ose;
+        t[i].byte_offsets(H, W, esz, onw, one, osw, ose);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             v[i][c][0] = buffer_load_px1<T>(r_img, onw, c * plane * esz);
@@ -471,15 +460,9 @@ __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ im
         const __amdgpu_buffer_rsrc_t r_out = uniform_rsrc(out + static_cast<int64_t>(b) * NC * plane, NC * plane * esz);
 #pragma unroll
         for (int i = 0; i < PX; ++i) {
-            const float wnw = ax[i] * ay[i], wne = bx[i] * ay[i], wsw = ax[i] * by[i], wse = bx[i] * by[i];
 #pragma unroll
-            for (int c = 0; c < NC; ++c) {
-                float acc = v[i][c][0] * wnw;   // absent taps contribute exact zeros
-                acc += v[i][c][1] * wne;
-                acc += v[i][c][2] * wsw;
-                acc += v[i][c][3] * wse;
-                buffer_store_px<T>(r_out, pix[i] * esz, c * plane * esz, acc);
-            }
+            for (int c = 0; c < NC; ++c)
+                buffer_store_px<T>(r_out, pix[i] * esz, c * plane * esz, t[i].blend(v[i][c][0], v[i][c][1], v[i][c][2], v[i][c][3]));
         }
     } else {
         const __amdgpu_buffer_rsrc_t r_gf = uniform_rsrc(gflow + static_cast<int64_t>(b) * 2 * plane, 2 * plane * fsz);
@@ -495,9 +478,8 @@ __global__ __launch_bounds__(256) void warp_fewc_kernel(const T *__restrict__ im
                                            g[k][i], px, py);
                 sx += px; sy += py;
             }
-            // autograd order: grad_grid = mult * sum ; through norm_grid: / (size-1) then * 2.0
-            buffer_store_px<F>(r_gf, pix[i] * fsz, 0, mx[i] * sx / static_cast<float>(W - 1) * 2.0f);
-            buffer_store_px<F>(r_gf, pix[i] * fsz, plane * fsz, my[i] * sy / static_cast<float>(H - 1) * 2.0f);
+            buffer_store_px<F>(r_gf, pix[i] * fsz, 0, flow_grad_out(mx[i], sx, W));
+            buffer_store_px<F>(r_gf, pix[i] * fsz, plane * fsz, flow_grad_out(my[i], sy, H));
         }
     }
 #endif

@@ -1,6 +1,9 @@
 // warp_common.h -- device helpers shared by the warp translation units (warp.hip: fp32 / general kernels,
-// warp16.hip: the 16-bit kernels with two elements per lane).  Everything lives in an anonymous namespace: each
-// translation unit gets its own copy (g_warp_zero included).
+// warp16.hip: the 16-bit kernels with two elements per lane) and by every other kernel that samples what flow_warp
+// writes (warp_corr.hip, occlusion.hip, metrics.hip: warp_sad, reproject.hip): the sample position (source_coord), the
+// bilinear taps of a position (Bilinear: the one home of the tap contract), the grad_flow terms and their closing line
+// (flow_grad_terms, flow_grad_out), the tap fetches (tap_ptr, load_taps), the backward context and the LDS window.
+// Everything lives in an anonymous namespace: each translation unit gets its own copy (g_warp_zero included).
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -228,6 +231,81 @@ __device__ __forceinline__ void flow_grad_terms(A vnw, A vne, A vsw, A vse, A ax
     gix = fma(fma(vne - vnw, ay, (vse - vsw) * fy), g, gix);
     giy = fma(fma(vsw - vnw, ax, (vse - vne) * fx), g, giy);
 }
+// The closing line of every grad_flow role, in autograd's order: grad_grid = mult * sum; through norm_grid: / (size - 1),
+// then * 2.0
+template <typename A>
+__device__ __forceinline__ A flow_grad_out(A mult, A sum, int size) {
+    return mult * sum / static_cast<A>(size - 1) * A(2.0);
+}
+
+[[maybe_unused]] constexpr int kDeadOffset = static_cast<int>(0x80000000u);   // buffer offset that reads 0 / drops a store
+
+// ---- the tap contract ---------------------------------------------------------------------
+// The bilinear taps of ONE sample position (px, py), after unnormalise + padding: the definition of the fractions, the
+// four weights, the north-west tap index, the in-image flags and the order of the four products (nw, ne, sw, se) FOR
+// THE KERNELS LISTED HERE: warp_bwd_kernel, warp_fewc_kernel, warp_context_kernel, warp_corr, occlusion, warp_sad,
+// reproject.  The kernels of the benched step -- warp_fwd_kernel, warp_fwd_staged_kernel, Px of warp16.hip, and in
+// warp_bwd_tile_kernel flow_role_staged, flow_pixel_direct, the strip role, classify and flow_role16 -- spell the same
+// arithmetic out (converted, the step measured 1 - 3 % slower for no reason found in their assembly) and
+// must be kept in step with this type BY HAND; the bit-for-bit tests of tests/test_warp_gpu.py, test_metrics_gpu.py,
+// test_occlusion_gpu.py, test_depth_recon_gpu.py and test_pwchead_gpu.py pin them to each other.  It holds the position
+// and its floor; everything else is an accessor computed where it is asked for: a site keeps its own order of evaluation
+// (the compiler's schedule follows it) and pays for nothing it does not use.  How a tap is FETCHED -- load_taps,
+// tap_ptr, a buffer resource, an LDS window -- stays the kernel's business.
+// A default-constructed one sits at (-2, -2): no tap inside any image (dead).  Its weights are (1, 0, 0, 0), NOT zeros, so
+// its blend is not zero unless the taps are: a lane that holds one must not store what it blends unless its four taps read
+// zeros (warp_corr's absent window pixels: all four offsets are kDeadOffset).
+template <typename A> struct Bilinear {
+    A px, py;      // the sample position
+    A x0f, y0f;    // its floor
+    __device__ __forceinline__ Bilinear(A px_ = A(-2), A py_ = A(-2)) : px(px_), py(py_), x0f(floor(px_)), y0f(floor(py_)) {}
+    // fractions: x1f - px, px - x0f with x1f = x0f + 1 (and the same in y)
+    __device__ __forceinline__ A ax() const { return (x0f + A(1)) - px; }
+    __device__ __forceinline__ A bx() const { return px - x0f; }
+    __device__ __forceinline__ A ay() const { return (y0f + A(1)) - py; }
+    __device__ __forceinline__ A by() const { return py - y0f; }
+    __device__ __forceinline__ A wnw() const { return ax() * ay(); }
+    __device__ __forceinline__ A wne() const { return bx() * ay(); }
+    __device__ __forceinline__ A wsw() const { return ax() * by(); }
+    __device__ __forceinline__ A wse() const { return bx() * by(); }
+    // the north-west tap
+    __device__ __forceinline__ int x0() const { return tap_index(static_cast<float>(x0f)); }
+    __device__ __forceinline__ int y0() const { return tap_index(static_cast<float>(y0f)); }
+    // which of the four taps are inside the image
+    __device__ __forceinline__ void inside(int H, int W, bool &nw, bool &ne, bool &sw, bool &se) const {
+        const int x = x0(), y = y0();
+        const bool okx0 = x >= 0 && x < W, okx1 = x + 1 >= 0 && x + 1 < W;
+        const bool oky0 = y >= 0 && y < H, oky1 = y + 1 >= 0 && y + 1 < H;
+        nw = oky0 && okx0; ne = oky0 && okx1; sw = oky1 && okx0; se = oky1 && okx1;
+    }
+    // no tap is inside the image
+    __device__ __forceinline__ bool dead(int H, int W) const { return !(x0() >= -1 && x0() <= W - 1 && y0() >= -1 && y0() <= H - 1); }
+    // the sample from the four tap values; absent taps contribute exact zeros
+    __device__ __forceinline__ A blend(A vnw, A vne, A vsw, A vse) const {
+        A acc = vnw * wnw();
+        acc += vne * wne();
+        acc += vsw * wsw();
+        acc += vse * wse();
+        return acc;
+    }
+    // Offsets of the four taps inside one plane, form 1: 32-bit BYTE offsets for a buffer resource, kDeadOffset (reads
+    // 0) for an absent tap.  |x0|, |y0| <= 2^24: the product may wrap (unsigned arithmetic: defined), but only in-image
+    // taps use it.
+    __device__ __forceinline__ void byte_offsets(int H, int W, int esz, int &onw, int &one, int &osw, int &ose) const {
+        bool nw, ne, sw, se;
+        inside(H, W, nw, ne, sw, se);
+        const int o00 = static_cast<int>((static_cast<unsigned>(y0()) * static_cast<unsigned>(W) + static_cast<unsigned>(x0())) * esz);
+        onw = nw ? o00 : kDeadOffset; one = ne ? o00 + esz : kDeadOffset;
+        osw = sw ? o00 + W * esz : kDeadOffset; ose = se ? o00 + (W + 1) * esz : kDeadOffset;
+    }
+    // Form 2: ELEMENT offsets clamped into the plane, for tap_ptr(plane + offset, flag): an offset is formed only from
+    // coordinates inside the image, absent taps read tap_ptr's block of zeros.
+    __device__ __forceinline__ void clamped_offsets(int H, int W, int64_t &onw, int64_t &one, int64_t &osw, int64_t &ose) const {
+        const int cx0 = min(max(x0(), 0), W - 1), cx1 = min(max(x0() + 1, 0), W - 1);
+        const int64_t r0 = static_cast<int64_t>(min(max(y0(), 0), H - 1)) * W, r1 = static_cast<int64_t>(min(max(y0() + 1, 0), H - 1)) * W;
+        onw = r0 + cx0; one = r0 + cx1; osw = r1 + cx0; ose = r1 + cx1;
+    }
+};
 
 // ---- forward, LDS-staged window -------------------------------------------------------
 // The direct gather above moves every 128-byte line a wave's taps touch from L2 to the CU
@@ -246,7 +324,6 @@ __device__ __forceinline__ void flow_grad_terms(A vnw, A vne, A vsw, A vse, A ax
 [[maybe_unused]] constexpr int kStageCap = 8192;   // floats of LDS window per workgroup
 [[maybe_unused]] constexpr int kStageMaxArea = 4096;   // largest window of ONE channel (1024 16-byte cells)
 constexpr int kStageRows = 4;     // strips (waves) per workgroup, stacked vertically
-[[maybe_unused]] constexpr int kDeadOffset = static_cast<int>(0x80000000u);   // buffer offset that reads 0 / drops a store
 
 // Wave-wide min / max through DPP row shifts and row broadcasts; the result is wave-uniform.  Round 6: the six steps are
 // v_min_i32_dpp / v_max_i32_dpp themselves (inline asm: the compiler makes v_mov + v_mov_dpp + v_min of every

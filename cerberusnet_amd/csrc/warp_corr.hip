@@ -6,7 +6,7 @@
 //
 // The warped feature map is never written: a workgroup samples the (TH + 8) x (TW + 8) window of its 8 x 32 output tile
 // straight into LDS -- the bilinear taps of every window pixel with the warp kernels' own coordinate arithmetic
-// (warp_common.h: source_coord, the reference's fp32 rounding order), rounded through the storage type as the stand-alone
+// (warp_common.h: source_coord, the reference's fp32 rounding order; Bilinear: weights, byte offsets, the order of the sum), rounded through the storage type as the stand-alone
 // warp's output would be -- four channels at a time (the next four's taps in flight meanwhile), and correlates it against f1 from there: a thread owns one output
 // pixel and its 81 accumulators.  Window pixels outside the image are the correlation's zero padding.
 //
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void warp_corr_fwd_kernel(
     const __amdgpu_buffer_rsrc_t r1 = uniform_rsrc(f1 + static_cast<int64_t>(b) * C * plane, C * plane * esz);
 
     // ---- the thread's window pixels: sample position, tap offsets, weights (once for all channels) ----
-    float wnw[kFWN], wne[kFWN], wsw[kFWN], wse[kFWN];
+    Bilinear<float> smp[kFWN];   // (default: no tap, the offsets below stay dead -- the blend is an exact zero)
     int onw[kFWN], one[kFWN], osw[kFWN], ose[kFWN], slot[kFWN];
 #pragma unroll
     for (int k = 0; k < kFWN; ++k) {
@@ -63,26 +63,13 @@ __global__ __launch_bounds__(256) void warp_corr_fwd_kernel(
         const int gx = x0t - kFD + wx, gy = y0t - kFD + wy;
         const bool in = e < kFWH * kFWW && gx >= 0 && gx < W && gy >= 0 && gy < H;   // else: the correlation's zero padding
         slot[k] = e < kFWH * kFWW ? wy * kFWP + wx : -1;
-        wnw[k] = wne[k] = wsw[k] = wse[k] = 0.f;
         onw[k] = one[k] = osw[k] = ose[k] = kDeadOffset;
         if (in) {
             const F *fl = flow + static_cast<int64_t>(b) * 2 * plane + gy * W + gx;
             const Coord<float> cx = source_coord<float>(gx, static_cast<float>(ld(fl)), W, pad_mode);
             const Coord<float> cy = source_coord<float>(gy, static_cast<float>(ld(fl + plane)), H, pad_mode);
-            const float x0f = floorf(cx.pos), y0f = floorf(cy.pos);
-            const float x1f = x0f + 1.f, y1f = y0f + 1.f;
-            wnw[k] = (x1f - cx.pos) * (y1f - cy.pos);
-            wne[k] = (cx.pos - x0f) * (y1f - cy.pos);
-            wsw[k] = (x1f - cx.pos) * (cy.pos - y0f);
-            wse[k] = (cx.pos - x0f) * (cy.pos - y0f);
-            const int x0 = tap_index(x0f), y0 = tap_index(y0f);
-            const bool okx0 = x0 >= 0 && x0 < W, okx1 = x0 + 1 >= 0 && x0 + 1 < W;
-            const bool oky0 = y0 >= 0 && y0 < H, oky1 = y0 + 1 >= 0 && y0 + 1 < H;
-            const int o00 = static_cast<int>((static_cast<unsigned>(y0) * static_cast<unsigned>(W) + static_cast<unsigned>(x0)) * esz);
-            onw[k] = (oky0 && okx0) ? o00 : kDeadOffset;
-            one[k] = (oky0 && okx1) ? o00 + esz : kDeadOffset;
-            osw[k] = (oky1 && okx0) ? o00 + W * esz : kDeadOffset;
-            ose[k] = (oky1 && okx1) ? o00 + (W + 1) * esz : kDeadOffset;
+            smp[k] = Bilinear<float>(cx.pos, cy.pos);
+            smp[k].byte_offsets(H, W, esz, onw[k], one[k], osw[k], ose[k]);
         }
     }
 
@@ -120,10 +107,7 @@ __global__ __launch_bounds__(256) void warp_corr_fwd_kernel(
             if (slot[k] >= 0) {
 #pragma unroll
                 for (int i = 0; i < kFCC; ++i) {
-                    float s = v[k][i][0] * wnw[k];     // the warp kernels' order (warp.hip: warp_fwd_kernel)
-                    s += v[k][i][1] * wne[k];
-                    s += v[k][i][2] * wsw[k];
-                    s += v[k][i][3] * wse[k];
+                    float s = smp[k].blend(v[k][i][0], v[k][i][1], v[k][i][2], v[k][i][3]);
                     if constexpr (esz == 2) {            // the stand-alone warp stores T: the correlation then reads the rounded value
                         T t;
                         st(&t, s);
