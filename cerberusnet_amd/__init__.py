@@ -24,6 +24,10 @@ from .ops_ocr import object_attention, spatial_gather
 from . import ops_detr  # noqa: F401  (registers torch.ops.cerberus_detr.*)
 from .loss_functions.detr_loss import DetrLoss, detr_set_loss
 from .nnet_models.detr import HungarianMatcher, pad_targets
+from . import ops_pdl  # noqa: F401  (registers torch.ops.cerberus_pdl.*)
+from .nnet_models.aspp import ASPP
+from .nnet_models.deeplab_panoptic import PanopticDeepLabDecoder, SinglePanopticDeepLabDecoder, SinglePanopticDeepLabHead
+from .ops_pdl import dwconv5x5, upcat_dwconv5x5
 from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
 from .utilities.panoptic_targets import PanopticTargetGenerator, panoptic_targets
 
@@ -37,4 +41,6 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "PanopticMetric", "deeplab_panoptic_loss", "DeeplabPanopticLoss", "panoptic_targets", "PanopticTargetGenerator", "ops",
            "BNReLU", "scale_as", "SpatialGather_Module", "ObjectAttentionBlock", "SpatialOCR_Module", "OCR_block", "OCRNetHead",
            "spatial_gather", "object_attention", "ops_ocr",
-           "ops_detr", "DetrLoss", "detr_set_loss", "HungarianMatcher", "pad_targets"]
+           "ops_detr", "DetrLoss", "detr_set_loss", "HungarianMatcher", "pad_targets",
+           "ops_pdl", "dwconv5x5", "upcat_dwconv5x5", "ASPP", "SinglePanopticDeepLabDecoder", "SinglePanopticDeepLabHead",
+           "PanopticDeepLabDecoder"]

@@ -676,6 +676,34 @@ int cerberus_detr_set_loss_backward(const void *logits, const void *boxes, const
                                     const void *wsum, const void *grad_losses, void *grad_logits, void *grad_boxes, int N, int B, int Q,
                                     int C1, int Tmax, int dtype, void *stream);
 
+/* The Panoptic-DeepLab decoder head's own step (additions only: no ABI bump): the depthwise 5x5 convolution (cross-correlation,
+ * stride 1, zero padding 2, no bias) of nnet_models/deeplab_panoptic.py, fp32 NCHW, over the virtual tensor
+ *     in = cat(interpolate(low, (H,W), bilinear, align_corners=True), skip)        (B,Ca+Cb,H,W)
+ * which is never written to memory.  Ca == 0 is the plain convolution of `skip` (low, h, w and grad_low are ignored).
+ *   low (B,Ca,h,w), skip (B,Cb,H,W), weight (Ca+Cb,1,5,5) -> out (B,Ca+Cb,H,W);  Ca >= 0, Cb >= 1; h == H, h == 1 and
+ *   non-integer ratios are legal.  The upsample uses ATen's fp32 operation order: scale = (float)(h-1)/(H-1) (0 when H == 1),
+ *   src = scale * y, i0 = (int)src, i1 = min(i0+1, h-1), lambda = src - i0; the same for x.
+ * Backward: any of grad_low (B,Ca,h,w), grad_skip (B,Cb,H,W), grad_weight (Ca+Cb,1,5,5) may be NULL: that gradient is not
+ * computed and its launch is skipped (at least one must be asked for).  At most three launches: the stencil with the flipped
+ * weights over grad_out, which also leaves one float64 partial of every grad_weight element per tile of 32 x 64 pixels (the input
+ * window is built again from low / skip); grad_low as a gather (a low-res pixel sums the high-res pixels that sampled it, rows then
+ * columns ascending); the fold of the partials.  No floating-point atomics: the same bits on every run, in a replayed graph and
+ * for any alignment of the tensor pointers (4 bytes are required; rows that start on 16 bytes take 16-byte loads and stores).
+ * Every element of every output asked for is written (no zero-fill needed); no host synchronisation: capturable.
+ *   workspace : cerberus_pdl_workspace_bytes(B,Ca,Cb,H,W) bytes (0 for sizes the calls reject), 16-byte aligned: the gradient of
+ *               the upsampled channels, B Ca H W floats padded to 16 bytes, then (Ca+Cb) x 25 x B x tiles float64 partials,
+ *               tiles = ceil(H/32) ceil(W/64).  The forward needs none.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; B, Cb, H or W <= 0, Ca < 0, h or w <= 0 with Ca > 0
+ * CERB_EINVAL; H W > 2^31 - 1025, more than 65535 tiles, or B (Ca+Cb), B tiles, h w past 2^31 - 1 CERB_ETOOLARGE; a null pointer
+ * (but for the optional ones above) or one that is not 4-byte aligned, a workspace that is misaligned or too small CERB_EINVAL --
+ * all before any launch. */
+int64_t cerberus_pdl_workspace_bytes(int B, int Ca, int Cb, int H, int W);
+int cerberus_pdl_dwconv_forward(const void *low, const void *skip, const void *weight, void *out, int B, int Ca, int Cb, int h, int w,
+                                int H, int W, int dtype, void *stream);
+int cerberus_pdl_dwconv_backward(const void *grad_out, const void *low, const void *skip, const void *weight, void *grad_low,
+                                 void *grad_skip, void *grad_weight, void *workspace, int64_t workspace_bytes, int B, int Ca, int Cb,
+                                 int h, int w, int H, int W, int dtype, void *stream);
+
 /* The device side of the panoptic metric (additions only: no ABI bump): what the reference's PanopticMetric
  * (nnet_training/statistics/panoptic.py) and utilities/panoptic_post_processing.py do to the centre heat map, the offset map and
  * the id / class maps of every image.  Forward only, no host synchronisation, no floating-point atomics: capturable and
