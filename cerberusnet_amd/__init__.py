@@ -28,6 +28,10 @@ from . import ops_pdl  # noqa: F401  (registers torch.ops.cerberus_pdl.*)
 from .nnet_models.aspp import ASPP
 from .nnet_models.deeplab_panoptic import PanopticDeepLabDecoder, SinglePanopticDeepLabDecoder, SinglePanopticDeepLabHead
 from .ops_pdl import dwconv5x5, upcat_dwconv5x5
+from . import ops_attn  # noqa: F401  (registers torch.ops.cerberus_attn.*)
+from .nnet_models.detr import (MLP, DetrSegmHead, PositionEmbeddingLearned, PositionEmbeddingSine, Transformer, TransformerDecoder,
+                               TransformerDecoderLayer, TransformerEncoder, TransformerEncoderLayer, build_position_encoding)
+from .ops_attn import detr_attention
 from .statistics import DepthMetric, MetricBase, OpticFlowMetric, PanopticMetric, SegmentationMetric
 from .utilities.panoptic_targets import PanopticTargetGenerator, panoptic_targets
 
@@ -43,4 +47,7 @@ __all__ = ["Correlation", "CorrelationFunction", "CorrelationTorch", "flow_warp"
            "spatial_gather", "object_attention", "ops_ocr",
            "ops_detr", "DetrLoss", "detr_set_loss", "HungarianMatcher", "pad_targets",
            "ops_pdl", "dwconv5x5", "upcat_dwconv5x5", "ASPP", "SinglePanopticDeepLabDecoder", "SinglePanopticDeepLabHead",
-           "PanopticDeepLabDecoder"]
+           "PanopticDeepLabDecoder",
+           "ops_attn", "detr_attention", "Transformer", "TransformerEncoder", "TransformerDecoder", "TransformerEncoderLayer",
+           "TransformerDecoderLayer", "PositionEmbeddingSine", "PositionEmbeddingLearned", "build_position_encoding", "MLP",
+           "DetrSegmHead"]

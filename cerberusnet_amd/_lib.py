@@ -102,6 +102,9 @@ PROTOTYPES = {
     "cerberus_pdl_workspace_bytes": (_I64, [_I] * 5),
     "cerberus_pdl_dwconv_forward": (_I, [_P] * 4 + [_I] * 8 + [_P]),
     "cerberus_pdl_dwconv_backward": (_I, [_P] * 8 + [_I64] + [_I] * 8 + [_P]),
+    "cerberus_attn_forward": (_I, [_P] * 8 + [_I] * 5 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_attn_backward": (_I, [_P] * 12 + [_I] * 5 + [ctypes.c_float, ctypes.c_float, _I, _P]),
+    "cerberus_attn_dropout_keep": (_I, [_P, _P] + [_I] * 4 + [ctypes.c_float, _P]),
     "cerberus_edge_smoothness_workspace_bytes": (_I64, [_I] * 3),
     "cerberus_edge_smoothness_forward": (_I, [_P, _P, _P, _P, _I64] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),
     "cerberus_edge_smoothness_backward": (_I, [_P, _P, _P, _P] + [_I] * 5 + [ctypes.c_float, _I, _I, _P]),

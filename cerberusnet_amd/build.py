@@ -22,7 +22,7 @@ ARCH = "gfx950"
 SOURCES = ["api.hip", "corr_generic.hip", "corr_d4.hip", "corr_d4_bwd.hip", "corr_strip.hip", "corr_coarse.hip", "corr_mfma.hip",
            "corr_grad_prep.hip", "warp.hip", "warp16.hip", "warp_corr.hip", "upsample.hip", "photometric.hip", "census.hip",
            "occlusion.hip", "reproject.hip", "seg_loss.hip", "seg_ohem.hip", "depth_loss.hip", "metrics.hip", "rmi_loss.hip", "panoptic.hip",
-           "panoptic_train.hip", "ocr_head.hip", "detr_loss.hip", "pdl_head.hip"]
+           "panoptic_train.hip", "ocr_head.hip", "detr_loss.hip", "pdl_head.hip", "detr_attn.hip"]
 # lib/libcerberus_hip_experiments.so (-DCERB_EXPERIMENTS): the product's sources + the measured-and-rejected kernels that no
 # dispatch rule selects (forward variants 1, 2, 8, 17; backward 2, 6, 7, 9, 10; the two-item strip backward) -- kept for the
 # record and tested through CERBERUS_HIP_LIB (tests/test_experiments_gpu.py), never loaded by default

@@ -6,8 +6,12 @@ from .ocr_utils import BNReLU, ObjectAttentionBlock, SpatialGather_Module, Spati
 from .ocrnet import OCR_block, OCRNetHead
 from .aspp import ASPP
 from .deeplab_panoptic import PanopticDeepLabDecoder, SinglePanopticDeepLabDecoder, SinglePanopticDeepLabHead
+from .detr import (MLP, DetrSegmHead, PositionEmbeddingLearned, PositionEmbeddingSine, Transformer, TransformerDecoder,
+                   TransformerDecoderLayer, TransformerEncoder, TransformerEncoderLayer, build_position_encoding)
 
 __all__ = ["PWCNetHead", "FlowEstimatorDense", "FlowEstimatorLite", "ContextNetwork",
            "HighResolutionNet", "hrnet_config", "CerberusBase", "cerberus_flow_config",
            "BNReLU", "scale_as", "SpatialGather_Module", "ObjectAttentionBlock", "SpatialOCR_Module", "OCR_block", "OCRNetHead",
-           "ASPP", "SinglePanopticDeepLabDecoder", "SinglePanopticDeepLabHead", "PanopticDeepLabDecoder"]
+           "ASPP", "SinglePanopticDeepLabDecoder", "SinglePanopticDeepLabHead", "PanopticDeepLabDecoder",
+           "Transformer", "TransformerEncoder", "TransformerDecoder", "TransformerEncoderLayer", "TransformerDecoderLayer",
+           "PositionEmbeddingSine", "PositionEmbeddingLearned", "build_position_encoding", "MLP", "DetrSegmHead"]

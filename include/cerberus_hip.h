@@ -704,6 +704,35 @@ int cerberus_pdl_dwconv_backward(const void *grad_out, const void *low, const vo
                                  void *grad_skip, void *grad_weight, void *workspace, int64_t workspace_bytes, int B, int Ca, int Cb,
                                  int h, int w, int H, int W, int dtype, void *stream);
 
+/* The DETR head's multi-head attention core (additions only: no ABI bump), csrc/detr_attn.hip: per batch entry b and head h, with
+ * D = 32 channels per head,
+ *     out = dropout(softmax(scale q k^T + key_padding_mask)) v
+ * fp32, flash-style: nothing of size Lq x Lk is written.  The tensors are read where F.linear leaves them:
+ *   q (Lq,B,H*D), k and v (Lk,B,H*D) -> out (Lq,B,H*D), lse (B,H,Lq): the log-sum-exp of every row of scale q k^T + mask, and
+ *   stats (B,H,Lq,2): that row's maximum and its sum of exp(. - maximum), which the backward recomputes the probabilities from
+ *   (exp(s - max) / sum as in the forward: exp(s - lse) would carry the rounding of lse and of s - lse, 2^-22 for a hundred keys).
+ *   key_padding_mask : (B,Lk) bytes or NULL; non-zero means the key is ignored.  A row whose keys are all ignored gives out = 0,
+ *                      lse = -inf and zero gradients (the stock chain gives NaN there).
+ *   seed             : ONE int64 in device memory (8-byte aligned), read by the kernels: no host read, capturable.  May be NULL
+ *                      when dropout_p == 0.  The keep decision is the stateless hash of csrc/attn_dropout.h over (seed, b H + h,
+ *                      query, key); kept probabilities are multiplied by 1 / (1 - dropout_p).
+ * Backward: any of grad_q (Lq,B,H*D), grad_k, grad_v (Lk,B,H*D) may be NULL (at least one must be asked for): grad_q NULL skips
+ * the query-owning launch, grad_k and grad_v both NULL skip the key-owning one.  At most three launches: delta = rowsum(grad_out *
+ * out), the key-owning kernel (grad_k, grad_v), the query-owning kernel (grad_q).  No atomics: the same bits on every run, in a
+ * replayed graph, whatever else is asked for, and for any 4-byte alignment of the tensor pointers.  Every element of every output
+ * asked for is written.
+ *   delta : scratch, B*H*Lq floats.
+ * cerberus_attn_dropout_keep writes the keep decisions as (B,H,Lq,Lk) bytes (1 = kept); dropout_p == 0 keeps everything.
+ * Errors: unknown dtype CERB_EDTYPE; fp16 / bf16 / fp64 CERB_EUNSUPPORTED; Lq, Lk, B, H or D <= 0, dropout_p outside [0,1), a
+ * scale that is not finite CERB_EINVAL; D != 32 CERB_EUNSUPPORTED; B H or max(Lq,Lk) B H D past 2^31 - 1, or a launch of 2^32 threads or more
+ * CERB_ETOOLARGE; a null pointer (but for the optional ones above) or a misaligned one CERB_EINVAL -- all before any launch. */
+int cerberus_attn_forward(const void *q, const void *k, const void *v, const void *key_padding_mask, const void *seed, void *out,
+                          void *lse, void *stats, int Lq, int Lk, int B, int H, int D, float scale, float dropout_p, int dtype, void *stream);
+int cerberus_attn_backward(const void *grad_out, const void *q, const void *k, const void *v, const void *key_padding_mask,
+                           const void *seed, const void *out, const void *stats, void *grad_q, void *grad_k, void *grad_v, void *delta,
+                           int Lq, int Lk, int B, int H, int D, float scale, float dropout_p, int dtype, void *stream);
+int cerberus_attn_dropout_keep(const void *seed, void *keep, int B, int H, int Lq, int Lk, float dropout_p, void *stream);
+
 /* The device side of the panoptic metric (additions only: no ABI bump): what the reference's PanopticMetric
  * (nnet_training/statistics/panoptic.py) and utilities/panoptic_post_processing.py do to the centre heat map, the offset map and
  * the id / class maps of every image.  Forward only, no host synchronisation, no floating-point atomics: capturable and
